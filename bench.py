@@ -15,6 +15,11 @@ acquired channels are sharded round-robin over the ranks, and every step ends wi
 the result gathers (RCCL over xGMI; the TckResultCT rows never leave HBM), so every
 rank holds the full outputs. Timing is bracketed by barriers, the max over ranks
 is reported, `value` = all ranks' units / that time.
+
+A plain run sets up, warms up, times `--steps` steps, writes the last step's outputs
+if `--dump-outputs DIR` is given, and prints the line. `--full` adds the legs that
+take runs of their own after the timed region: the roofline's profiling pass and the
+counter evidence of profiles/, the acquisition's fp32 fast mode, the cpu_baseline.
 """
 from __future__ import annotations
 
@@ -106,9 +111,17 @@ def parse():
     ap.add_argument("--n10", type=int, default=40000, help="msToProcessCT_10ms")
     ap.add_argument("--skip", type=int, default=5000, help="file.skip (ms)")
     ap.add_argument("--datalen", type=int, default=20)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: the roofline's "
+                         "profiling pass and counter evidence, the acquisition's fp32 fast mode and the "
+                         "cpu_baseline leg (without it the line carries null in their places)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (Acquired, the TckResultCT buffers) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=1)
-    ap.add_argument("--no-profile-pass", action="store_true")
+    ap.add_argument("--no-profile-pass", action="store_true",
+                    help="with --full: skip the profiling pass and the fp32 fast mode")
     ap.add_argument("--workload", choices=["cfg2+3", "cfg4", "cfg5", "dist-selftest"], default="cfg2+3",
                     help="cfg2+3: the headline step (default); cfg4: BASELINE config 4, 32-PRN Urban "
                          "acquisition, PRNs sharded over the ranks; cfg5: BASELINE config 5, 32-channel "
@@ -222,6 +235,43 @@ def max_over_ranks(dist, local, x):
     return float(t.item())
 
 
+DUMP_BUDGET = 60 * 10 ** 6  # bytes of --dump-outputs in all (under 64 MB with the .npy headers)
+
+
+def acquired_arrays(A):
+    return {f"acq_{f}": np.asarray(getattr(A, f)) for f in ("sv", "SNR", "Doppler", "codedelay", "fineFreq")}
+
+
+def tracking_arrays(buf):
+    """The trackingCT buffers a raw=True caller holds: rec (channel x field x row; rows past
+    len are unused), len, countinx, the filled CN0 rows and the ACF taps where the run has them."""
+    def host(t):  # (rec / taps: torch tensors in HBM, or host arrays)
+        return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+
+    out = {"track_rec": host(buf.rec), "track_len": buf.len, "track_countinx": buf.countinx,
+           "track_CN0": buf.CN0[: buf.c.cn0_rows]}
+    if buf.taps is not None:
+        out["track_taps"] = host(buf.taps)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64. Where they exceed DUMP_BUDGET
+    together, each large array keeps a fixed seeded sample of its last axis (the rows in time),
+    sized in proportion, and <name>_columns.npy holds the sampled indices; the same arguments
+    give the same files' shapes and indices on every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET and a.nbytes > DUMP_BUDGET // 100:
+            keep = max(1, int(a.shape[-1] * 0.9 * DUMP_BUDGET / total))
+            idx = np.sort(np.random.default_rng(6102).choice(a.shape[-1], keep, replace=False))
+            np.save(os.path.join(path, name + "_columns.npy"), idx.astype(np.float64))
+            a = np.ascontiguousarray(a[..., idx])
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def sum_over_ranks(dist, local, x):
     if dist is None:
         return x
@@ -280,6 +330,8 @@ def run_cfg5(args, rank, world, local, dist, ctx):
     barrier(dist, local)
     elapsed = max_over_ranks(dist, local, time.perf_counter() - t0)
     total = sum_over_ranks(dist, local, float(units))
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, tracking_arrays(outs[0]))
     roof = None
     if not args.no_profile_pass:
         ctx.set_profiling(True)
@@ -370,6 +422,8 @@ def run_cfg4(args, rank, world, local, dist, ctx):
     barrier(dist, local)
     elapsed = max_over_ranks(dist, local, time.perf_counter() - t0)
     total = sum_over_ranks(dist, local, float(units))
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, acquired_arrays(A))
     # the acquisition model (16 B per hypothesis-sample) over this rank's correlation
     # time (the fine-frequency FFTs excluded, timed in acq_ms)
     roof = None
@@ -380,7 +434,7 @@ def run_cfg4(args, rank, world, local, dist, ctx):
                 "kernel": "acquisition correlator (fwd/inv P x 2000 FFT passes, fp64), rank 0",
                 "corr_ms_per_step": round(corr_ms / args.steps, 3),
                 "algorithmic_bytes_per_step": 16.0 * units / args.steps}
-        tj, prov = evidence(TRAFFIC_FILES_CFG4)
+        tj, prov = evidence(TRAFFIC_FILES_CFG4) if args.full else (None, None)
         if tj and world == 1:  # (bytes of one full 32-PRN call: the N=1 step)
             roof["traffic"] = tj.get("bytes_per_call")
             roof["traffic_kernels"] = {k: v["bytes_per_call"] for k, v in tj.get("kernels", {}).items()}
@@ -481,6 +535,8 @@ def run_dist_selftest(args):
 def main():
     global pkg
     args = parse()
+    if not args.full:  # a plain run: the timed steps and their line only
+        args.no_cpu = args.no_profile_pass = True
     # N ranks with no launcher: this process only spawns them (before any GPU or library import)
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -597,6 +653,8 @@ def run_headline(args, rank, world, local, dist, ctx, multi=None):
     units = sum_over_ranks(dist, local, float(acq_units + trk_units))
     nch = len(A.sv)
     mine = shards[rank]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {**acquired_arrays(A), **tracking_arrays(buf)})
     # the step's outputs, checked (not timed): the scenario's 8 SVs acquired, every channel
     # tracked to full length, the gathered TckResultCT complete on this rank
     full_len = [1000 + int(c) + args.n10 for c in buf.countinx]
@@ -728,7 +786,7 @@ def run_headline(args, rank, world, local, dist, ctx, multi=None):
                           "fine_ms": round(acq_fine_ms / args.steps, 3)} if acq_corr_ms else None),
         # what bounds the acquisition kernels (PMC counters + rocprofv3 averages of this
         # round's separate passes, tools/acq_bound.py; a PMC pass cannot run in this process)
-        "acq_kernel_bounds": acq_bounds(),
+        "acq_kernel_bounds": acq_bounds() if args.full else None,
         "acq_fp32_fast_mode": fast,
         "code": code_stamp(),
         "cpu_baseline": cpu,

@@ -2,7 +2,7 @@
 # beside the plain run: where the distributed step's extra acquisition time comes from
 set -o pipefail
 mkdir -p gpurun_out
-ARGS="--gpus 1 --steps 4 --warmup 1 --no-cpu"
+ARGS="--gpus 1 --steps 4 --warmup 1 --full --no-cpu"
 run() {  # name env...
   local n=$1; shift
   env "$@" timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \

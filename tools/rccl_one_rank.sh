@@ -3,7 +3,7 @@
 # NCCL_DEBUG=INFO shows RCCL's own init lines. Writes gpurun_out/rccl_*.json / .err.
 set -o pipefail
 mkdir -p gpurun_out
-ARGS="--gpus 1 --steps 2 --warmup 1 --no-cpu"
+ARGS="--gpus 1 --steps 2 --warmup 1 --full --no-cpu"
 timeout -k 10 300 python3 bench.py $ARGS > gpurun_out/rccl_plain.json 2> gpurun_out/rccl_plain.err || { tail -20 gpurun_out/rccl_plain.err; exit 1; }
 for be in nccl gloo; do
   BENCH_FORCE_DIST=1 BENCH_DIST_BACKEND=$be NCCL_DEBUG=INFO timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
