@@ -121,6 +121,16 @@ class GnssVtOut(C.Structure):
                 ("deltaPr", C.c_double), ("prRate", C.c_double), ("sv_vel", C.c_double * 3)]
 
 
+class GnssVtMcOut(C.Structure):
+    """gnss_vt_mc_out: gnss_vt_out's fields, then the 25-tap loop's 50 sums in Spacing order
+    (trackingVT_POS_updated_multicorrelator.m; additive within ABI v13)."""
+    _fields_ = GnssVtOut._fields_ + [("tap_i", C.c_double * MC_TAPS), ("tap_q", C.c_double * MC_TAPS)]
+
+
+# the structs added within an ABI version: name in include/gnss_mi355x.h -> mirror here (their
+# layout is checked like the older ones', tests/test_vt_mc_twin.py)
+ADDED_STRUCTS = {"gnss_vt_mc_out": "GnssVtMcOut"}
+
 # the vector half of trackingVT_POS_updated.m (ABI v10)
 VT_MAX_CH = 32
 EPH_SV_FIELDS = ["sqrta", "deltan", "toe", "M0", "ecc", "w", "Cus", "Cuc", "Crs", "Crc", "Cis", "Cic", "i0",
@@ -244,6 +254,20 @@ PROTOTYPES = {
     "gnss_tracking_vt": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal), C.POINTER(GnssTrack),
                                    C.c_int32, C.c_int32, C.POINTER(GnssVtChan), C.POINTER(GnssVtNav),
                                    C.POINTER(GnssVtOut), C.POINTER(GnssVtNavSol)]),
+    # trackingVT_POS_updated_multicorrelator.m (additive within ABI v13: detected by symbol)
+    "gnss_tracking_vt_mc_run": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal),
+                                          C.POINTER(GnssTrack), C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(GnssVtChan), C.POINTER(C.c_double), C.POINTER(GnssVtMcOut)]),
+    "gnss_tracking_vt_mc": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal), C.POINTER(GnssTrack),
+                                      C.c_int32, C.c_int32, C.POINTER(GnssVtChan), C.POINTER(GnssVtNav),
+                                      C.POINTER(GnssVtMcOut), C.POINTER(GnssVtNavSol)]),
+    "gnss_vt_mc_prepare": (C.c_int, [C.POINTER(GnssSignal), C.c_int32, C.POINTER(GnssVtChan), C.c_double,
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "gnss_vt_mc_nco_step": (C.c_int, [C.POINTER(GnssSignal), C.POINTER(GnssTrack), C.c_int32,
+                                      C.POINTER(GnssVtChan), C.c_double, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(GnssVtMcOut)]),
+    "gnss_vt_mc_nav_update": (C.c_int, [C.POINTER(GnssVtNav), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(GnssVtNavSol)]),
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libgnss_mi355x.so")

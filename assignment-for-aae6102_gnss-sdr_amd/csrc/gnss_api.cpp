@@ -31,6 +31,7 @@
 
 #include "gnss_internal.h"
 #include "group.h"
+#include "vt_mc.h"
 
 using namespace gnss;
 
@@ -2744,6 +2745,238 @@ int gnss_tracking_vt(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg
     ctx->timing.track_kernel_ms = kernel_ms;  // (int8 records: summed in profiling mode only)
     ctx->timing.track_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count();
     return result;
+}
+
+namespace {
+// trackingVT_POS_updated_multicorrelator.m:151-609, the 25-tap loop behind gnss_tracking_vt_mc_run
+// (nav == nullptr: each step's code frequency is the caller's, series[s * n + i]) and
+// gnss_tracking_vt_mc (the EKF predicts it, :172-218, and takes the step's discriminators,
+// :472-609, with prr_measured from carrFreq - IF). Per step the host sizes each channel's read
+// and its 25 colons (vt_mc_prepare), clears the read against the file's length and the staged
+// window, launches the correlator once for all channels (vt_mc_step_kernel; int16 records: the
+// read's integer sums first), waits for the step's number in coherent host memory
+// (wait_posted) and runs each channel's scalar end on the 50 sums (vt_mc_finish). The channel
+// states stay on the host. A channel whose step fails gets the status in its record and reads
+// nothing; under the EKF the loop ends at that step, else the channel sits the later steps out.
+int vt_mc_loop(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg, const gnss_track* tr, int pdi, int n,
+               int nsteps, gnss_vt_chan* chans, const double* series, gnss_vt_nav* nav, gnss_vt_mc_out* out,
+               gnss_vt_navsol* sol)
+{
+    ctx->err.clear();
+    ctx->timing = gnss_timing{};
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int prec = file->dataPrecision, dtyp = file->dataType;
+    if (!((prec == 1 && (dtyp == 1 || dtyp == 2)) || (prec == 2 && dtyp == 2)))
+        return fail(ctx, GNSS_EARG, "vector tracking: int8 I/Q, int8 real or int16 I/Q records");
+    const int bps = prec * dtyp;
+    const int64_t flen = file_length(file);
+    if (flen < 0) return fail(ctx, GNSS_EIO, "cannot open IF record");
+    for (int i = 0; i < n; i++) {
+        if (chans[i].prn < 1 || chans[i].prn > 51) return fail(ctx, GNSS_EARG, "bad PRN");
+        if (nav && chans[i].prn != nav->prn[i]) return fail(ctx, GNSS_EARG, "chans[i].prn != nav->prn[i]");
+        if (chans[i].file_ptr < 0 || chans[i].file_ptr % bps) return fail(ctx, GNSS_EARG, "file_ptr");
+        if (chans[i].index_int < 0 || chans[i].index_int > 19 || chans[i].snrIndex < 1)
+            return fail(ctx, GNSS_EARG, "C/N0 state (index_int 0..19, snrIndex >= 1)");
+        if (!(chans[i].codeFreq > 0)) return fail(ctx, GNSS_EARG, "code frequency must be positive");
+    }
+    for (int64_t k = 0; series && k < (int64_t)nsteps * n; k++)
+        if (!(series[k] > 0)) return fail(ctx, GNSS_EARG, "code frequencies must be positive");
+    std::memset(out, 0, sizeof(gnss_vt_mc_out) * (size_t)nsteps * n);
+    // The IF window, as gnss_tracking_vt's: `span` steps at twice the nominal read from the
+    // earliest read, re-staged (at least as long as the step's reads need) when one leaves it.
+    const int64_t nominal = (int64_t)std::ceil(sg->codelength * pdi / (sg->codeFreqBasis / sg->Fs));
+    const int64_t span = std::min<int64_t>(nsteps, ctx->opt[GNSS_OPT_VT_SPAN] > 0 ? ctx->opt[GNSS_OPT_VT_SPAN] : kVtSpan);
+    IfWindow w;
+    auto restage = [&](int64_t lo, int64_t need_hi) -> int {
+        const int64_t hi = std::max(lo + (span * 2 * nominal + 64) * bps, need_hi);
+        w.own.release();
+        w.ptr = nullptr;
+        w.base = w.len = 0;
+        return stage_window(ctx, file, lo, std::min(hi, flen), w);
+    };
+    int64_t lo0 = INT64_MAX;
+    for (int i = 0; i < n; i++) lo0 = std::min(lo0, chans[i].file_ptr);
+    int st = restage(lo0, 0);
+    if (st) return st;
+    std::vector<unsigned> cab((size_t)n * 32);
+    for (int i = 0; i < n; i++) ca_bits(chans[i].prn, &cab[(size_t)i * 32]);
+    double t1, t2;
+    calc_loop_coef(tr->PLLBW, tr->PLLDamp, tr->PLLGain, t1, t2);
+    int nb = (int)std::min<int64_t>(std::max<int64_t>(1, (nominal + kVtMcStepSamples - 1) / kVtMcStepSamples),
+                                    GNSS_VT_MAX_BLOCKS);
+    if (ctx->opt[GNSS_OPT_VT_BLOCKS] > 0) nb = (int)ctx->opt[GNSS_OPT_VT_BLOCKS];
+    DevBuf d_ca, d_part, d_ticket, d_isum;
+    VtMcStepArgs B{};
+    B.sums = pinned_buffer<double>(ctx, "vtmc.sums", (size_t)kVtMcSums * n, hipHostMallocCoherent);
+    B.done = pinned_buffer<unsigned>(ctx, "vt.done", 1, hipHostMallocCoherent);
+    if (!B.sums || !B.done) return fail(ctx, GNSS_EDEVICE, "pinned VT step buffers");
+    __atomic_store_n(B.done, 0u, __ATOMIC_RELAXED);
+    HIP_TRY(d_ticket.alloc(ctx, "vt.ticket", sizeof(unsigned)));
+    HIP_TRY(hipMemsetAsync(d_ticket.p, 0, sizeof(unsigned), ctx->stream));
+    HIP_TRY(d_ca.alloc(ctx, "vt.ca", sizeof(unsigned) * cab.size()));
+    HIP_TRY(hipMemcpyAsync(d_ca.p, cab.data(), sizeof(unsigned) * cab.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(d_part.alloc(ctx, "vtmc.part", sizeof(double) * kVtMcSums * (size_t)n * nb));
+    if (prec == 2) HIP_TRY(d_isum.alloc(ctx, "vtmc.isum", sizeof(long long) * 2 * GNSS_VT_MAX_CH));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (cab is read by the copy until here)
+    B.ticket = d_ticket.as<unsigned>();
+    B.ca_bits = d_ca.as<unsigned>();
+    B.part = d_part.as<double>();
+    B.isum = prec == 2 ? d_isum.as<long long>() : nullptr;
+    B.Fs = sg->Fs;
+    B.fmt = prec == 2 ? 2 : (dtyp == 1 ? 1 : 0);
+    // k/Fs by Markstein's correction where it is the IEEE quotient (gnss_tracking_vt's check)
+    const int64_t kmax_rfs = 4 * nominal;
+    const double rfs = fast_div_exact(sg->Fs, kmax_rfs) ? 1.0 / sg->Fs : 0.0;
+    std::vector<gnss_vt_chan> hc(chans, chans + n);
+    std::vector<VtMcPrep> pk((size_t)n);
+    std::vector<int> bad((size_t)n, 0), stopped((size_t)n, 0);
+    std::vector<double> cf_new((size_t)n), dpr((size_t)n, 0.0), vel(3 * (size_t)n, 0.0), codeError((size_t)n),
+        carrFreq((size_t)n);
+    std::unique_ptr<VtGain> gain(nav ? new VtGain : nullptr);
+    Events ev;
+    double kernel_ms = 0;
+    int result = GNSS_OK, first = GNSS_OK;  // (first: the first channel status, and its message)
+    std::string first_err;
+    const auto t_loop = std::chrono::steady_clock::now();
+    for (int s = 0; s < nsteps && result == GNSS_OK; s++) {
+        // this step's code frequencies: the caller's, or the EKF's prediction from the read size
+        // the LAST code frequency gives (:155, :172-218)
+        for (int i = 0; i < n; i++) {
+            if (!nav) {
+                cf_new[(size_t)i] = series[(size_t)s * n + i];
+                continue;
+            }
+            const gnss_vt_chan& c = hc[(size_t)i];
+            const VtMcPrep p = vt_mc_prepare(sg->Fs, sg->codelength, pdi, c.remChip, c.codeFreq, c.codeFreq);
+            if (p.n < 1) {
+                result = fail(ctx, GNSS_EINDEX, "step %d channel %d: read size %lld", s + 1, i, (long long)p.n);
+                break;
+            }
+            double cf = c.codeFreq;
+            st = vt_nav_predict_at(nav, i, p.n, nullptr, &cf, &dpr[(size_t)i], &vel[3 * (size_t)i]);
+            if (st) {
+                result = fail(ctx, st, "step %d channel %d: svPosVel / trop_UNB3 failed", s + 1, i);
+                break;
+            }
+            cf_new[(size_t)i] = cf;
+        }
+        if (result) break;
+        // the step's reads: sized and cleared here, before anything is launched
+        int64_t need_lo = INT64_MAX, need_hi = 0;
+        for (int i = 0; i < n; i++) {
+            const gnss_vt_chan& c = hc[(size_t)i];
+            int b = 0;
+            if (stopped[(size_t)i]) {
+                pk[(size_t)i] = VtMcPrep{};
+            } else {
+                pk[(size_t)i] = vt_mc_prepare(sg->Fs, sg->codelength, pdi, c.remChip, c.codeFreq, cf_new[(size_t)i]);
+                b = !(cf_new[(size_t)i] > 0) ? GNSS_EARG : pk[(size_t)i].bad;
+                // a short fread makes `rawsignal .* carrsig` fail in MATLAB (:158-164, :290)
+                if (!b && c.file_ptr + pk[(size_t)i].n * bps > flen) b = GNSS_EIO;
+            }
+            bad[(size_t)i] = b;
+            if (!b && !stopped[(size_t)i]) {
+                need_lo = std::min(need_lo, c.file_ptr);
+                need_hi = std::max(need_hi, c.file_ptr + pk[(size_t)i].n * bps);
+            }
+        }
+        if (need_hi > 0 && !file->dev_data && (need_lo < w.base || need_hi > w.base + w.len)) {
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            st = restage(need_lo, need_hi);
+            if (st) return st;
+        }
+        int live = 0;
+        for (int i = 0; i < n; i++) {
+            const gnss_vt_chan& c = hc[(size_t)i];
+            const bool run = !bad[(size_t)i] && !stopped[(size_t)i];
+            if (run && (c.file_ptr < w.base || c.file_ptr + pk[(size_t)i].n * bps > w.base + w.len))
+                return fail(ctx, GNSS_EDEVICE, "step %d channel %d: the staged IF window [%lld, %lld) does not cover the read",
+                            s + 1, i, (long long)w.base, (long long)(w.base + w.len));
+            B.ns[i] = run ? pk[(size_t)i].n : 0;
+            B.off[i] = run ? c.file_ptr - w.base : 0;
+            B.f[i] = c.carrFreq;
+            B.phi0[i] = c.remCarrPhase;
+            B.rfs[i] = B.ns[i] - 1 <= kmax_rfs ? rfs : 0.0;
+            B.remChip[i] = c.remChip;
+            B.cps[i] = cf_new[(size_t)i] / sg->Fs;
+            live += run;
+        }
+        B.rec = reinterpret_cast<const uint8_t*>(w.ptr);
+        B.seq = (unsigned)s + 1;
+        if (live) {
+            if (ctx->profiling) HIP_TRY(hipEventRecord(ev.a, ctx->stream));
+            if (prec == 2) {
+                HIP_TRY(hipMemsetAsync(d_isum.p, 0, sizeof(long long) * 2 * GNSS_VT_MAX_CH, ctx->stream));
+                HIP_TRY(launch_vt_mc_isum(B.rec, B.off, B.ns, n, d_isum.as<long long>(), ctx->stream));
+            }
+            HIP_TRY(launch_vt_mc_step(B, n, nb, ctx->stream));
+            if (ctx->profiling) HIP_TRY(hipEventRecord(ev.b, ctx->stream));
+            if (nav) vt_nav_gain(*nav, gain.get());  // (needs the predictions only: beside the kernel)
+            if (ctx->profiling) HIP_TRY(hipStreamSynchronize(ctx->stream));
+            HIP_TRY(wait_posted(ctx->stream, B.done, B.seq));
+            if (ctx->profiling) kernel_ms += ev.ms();
+            ctx->timing.track_launches += 1;
+        }
+        for (int i = 0; i < n; i++) {  // each channel's scalar end
+            gnss_vt_mc_out& o = out[(size_t)s * n + i];
+            if (stopped[(size_t)i]) continue;
+            if (bad[(size_t)i]) {
+                o.status = bad[(size_t)i];
+                stopped[(size_t)i] = 1;
+                if (!first) {
+                    first = fail(ctx, o.status, "step %d channel %d stopped (replica index / read past EOF)", s + 1, i);
+                    first_err = ctx->err;
+                }
+                continue;
+            }
+            const double* sum = B.sums + (size_t)kVtMcSums * i;
+            vt_mc_finish(sg->Fs, sg->ms, pdi, bps, t1, t2, &hc[(size_t)i], pk[(size_t)i], cf_new[(size_t)i], sum,
+                         sum + kVtMcTaps, &o);
+            o.deltaPr = dpr[(size_t)i];
+            for (int k = 0; k < 3; k++) o.sv_vel[k] = vel[3 * (size_t)i + k];
+            ctx->timing.track_channel_samples += o.numSample;
+            codeError[(size_t)i] = o.codeError;
+            carrFreq[(size_t)i] = o.carrFreq;
+        }
+        // (the tracking half alone: the other channels go on while any is left)
+        if (first && (nav || std::find(stopped.begin(), stopped.end(), 0) == stopped.end())) break;
+        if (!nav) continue;
+        st = vt_nav_correct(nav, *gain, codeError.data(), cf_new.data(), carrFreq.data(), sol ? sol + s : nullptr, true);
+        if (st) result = fail(ctx, st, "step %d: navigation update failed (singular innovation covariance)", s + 1);
+    }
+    if (!result && first) {
+        ctx->err = first_err;
+        result = first;
+    }
+    std::copy(hc.begin(), hc.end(), chans);
+    ctx->timing.track_kernel_ms = kernel_ms;  // (summed in profiling mode only)
+    ctx->timing.track_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count();
+    return result;
+}
+}  // namespace
+
+int gnss_tracking_vt_mc_run(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg, const gnss_track* tr,
+                            int32_t pdi, int32_t n, int32_t nsteps, gnss_vt_chan* chans, const double* codeFreq_new,
+                            gnss_vt_mc_out* out)
+{
+    if (!ctx || !file || !sg || !tr || !chans || !codeFreq_new || !out || n < 1 || n > GNSS_VT_MAX_CH || pdi < 1 ||
+        nsteps < 1 || !(sg->Fs > 0) || !(sg->codeFreqBasis > 0))
+        return fail(ctx, GNSS_EARG, "bad arguments (n in 1..GNSS_VT_MAX_CH)");
+    return vt_mc_loop(ctx, file, sg, tr, pdi, n, nsteps, chans, codeFreq_new, nullptr, out, nullptr);
+}
+
+int gnss_tracking_vt_mc(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg, const gnss_track* tr, int32_t n,
+                        int32_t nsteps, gnss_vt_chan* chans, gnss_vt_nav* nav, gnss_vt_mc_out* out, gnss_vt_navsol* sol)
+{
+    if (!ctx || !file || !sg || !tr || !chans || !nav || !out || n < 1 || n > GNSS_VT_MAX_CH || n != nav->n ||
+        nsteps < 0 || !(sg->Fs > 0) || !(sg->codeFreqBasis > 0) || sg->Fs != nav->Fs)
+        return fail(ctx, GNSS_EARG, "bad arguments (n in 1..GNSS_VT_MAX_CH and equal to nav->n, signal as at gnss_vt_nav_init)");
+    if (nsteps == 0) {
+        ctx->err.clear();
+        ctx->timing = gnss_timing{};
+        return GNSS_OK;
+    }
+    return vt_mc_loop(ctx, file, sg, tr, nav->pdi, n, nsteps, chans, nullptr, nav, out, sol);
 }
 
 int gnss_ca_code(int prn, int8_t* out1023)

@@ -757,8 +757,9 @@ struct VtGain {
 };
 void vt_nav_gain(const gnss_vt_nav& v, VtGain* g);
 // ... and its measurement half: gnss_vt_nav_update == vt_nav_gain then vt_nav_correct
+// (minus_if: prr_measured from carrFreq - IF, the 25-tap loop's; else + IF)
 int vt_nav_correct(gnss_vt_nav* v, const VtGain& g, const double* codeError, const double* codeFreq,
-                   const double* carrFreq, gnss_vt_navsol* sol);
+                   const double* carrFreq, gnss_vt_navsol* sol, bool minus_if = false);
 // remChip after a step of n samples at code frequency codeFreq_new (vt_finish, :284): the read
 // sizes of a VT channel do not depend on its samples, so the next step's is known a step ahead
 inline double vt_remchip_next(double Fs, int pdi, double remChip, double codeFreq_new, int64_t n)

@@ -487,7 +487,7 @@ void gnss::vt_nav_gain(const gnss_vt_nav& v, VtGain* g)
 // :321, :380-382, :397-467: the measurements into newZ, the state update, the navigation
 // solution row, the next epoch's state and the measurement noise
 int gnss::vt_nav_correct(gnss_vt_nav* v, const VtGain& g, const double* codeError, const double* codeFreq,
-                         const double* carrFreq, gnss_vt_navsol* sol)
+                         const double* carrFreq, gnss_vt_navsol* sol, bool minus_if)
 {
     if (g.st) return g.st;
     const int n = v->n, N = 2 * n;
@@ -497,8 +497,11 @@ int gnss::vt_nav_correct(gnss_vt_nav* v, const VtGain& g, const double* codeErro
     double Z[2 * GNSS_VT_MAX_CH];
     for (int i = 0; i < n; i++) Z[i] = codeError[i] * cS / codeFreq[i];  // :321
     const double clkDrift = v->total_state[7];
+    // (trackingVT_POS_updated_multicorrelator.m:504 measures with carrFreq - signal.IF, the only
+    // line of the vector half in which the two loops differ)
+    const double IF = minus_if ? -v->IF : v->IF;
     for (int i = 0; i < n; i++) {
-        const double prr_meas = (carrFreq[i] + v->IF) * cS / v->cfg.Fc;  // :380
+        const double prr_meas = (carrFreq[i] + IF) * cS / v->cfg.Fc;  // :380
         Z[n + i] = g.prr_pred[i] - prr_meas - clkDrift + g.clkv[i];  // :382
     }
     double es[8];
@@ -657,6 +660,15 @@ int gnss_vt_nav_update(gnss_vt_nav* v, const double* codeError, const double* co
     gnss::VtGain g;
     gnss::vt_nav_gain(*v, &g);
     return gnss::vt_nav_correct(v, g, codeError, codeFreq, carrFreq, sol);
+}
+
+int gnss_vt_mc_nav_update(gnss_vt_nav* v, const double* codeError, const double* codeFreq, const double* carrFreq,
+                          gnss_vt_navsol* sol)
+{
+    if (!v || !codeError || !codeFreq || !carrFreq) return GNSS_EARG;
+    gnss::VtGain g;
+    gnss::vt_nav_gain(*v, &g);
+    return gnss::vt_nav_correct(v, g, codeError, codeFreq, carrFreq, sol, true);
 }
 
 }  // extern "C"

@@ -795,6 +795,40 @@ def trackingVT_POS_updated(file, signal, track, cmn, solu, Acquired, cnslxyz, ep
     reference's 3-D arrays) and R (:466). A channel error MATLAB raises on (a replica index
     out of range, a read past the end of the record) raises GnssError.
     """
+    R, sols, sv, nsteps = _vt_loop(file, signal, track, cmn, solu, Acquired, cnslxyz, eph, sbf, TckResult_Eph,
+                                   TckResultCT, navSolutionsCT, ctx, ALPHA_, BETA_, nsteps, True,
+                                   "gnss_tracking_vt", abi.GnssVtOut)
+    n = len(sv)
+    entries = {}
+    for i, p in enumerate(sv):
+        e = SimpleNamespace(**{k: R[k][:, i].astype(np.float64) for k in VT_FIELDS})
+        e.sv_vel = R["sv_vel"][:, i].copy()
+        for k in ("amplitude", "navi_data", "navi_dataL035"):
+            setattr(e, k, np.zeros(nsteps))
+        entries[p] = e
+    nsol = _navsol_arrays(sols, nsteps, n)
+    TckResultVT = StructArray(entries)
+    if return_cn0:
+        return TckResultVT, nsol, _cn0_rows(R, nsteps, n)
+    return TckResultVT, nsol
+
+
+def _cn0_rows(R, nsteps, n):
+    """CN0_VT (rows x channels) from the records' cn0_row / CN0."""
+    rows = int(R["cn0_row"].max()) if nsteps else 0
+    cn0 = np.zeros((rows, n))
+    for i in range(n):
+        m = R["cn0_row"][:, i] > 0
+        cn0[R["cn0_row"][:, i][m] - 1, i] = R["CN0"][:, i][m]
+    return cn0
+
+
+def _vt_loop(file, signal, track, cmn, solu, Acquired, cnslxyz, eph, sbf, TckResult_Eph, TckResultCT,
+             navSolutionsCT, ctx, ALPHA_, BETA_, nsteps, clamp, entry, OutT):
+    """The initialisation both vector-tracking loops share (trackingVT_POS_updated.m:66-132; the
+    25-tap loop's :63-123 is the same without the msStartTckVT clamp of the plain file's :106,
+    `clamp`), then the library's loop `entry` -> (records [nsteps][n] as a structured array of
+    OutT, the gnss_vt_navsol rows, the PRNs, nsteps)."""
     ctx = ctx or default_context()
     sv = [int(p) for p in np.atleast_1d(Acquired.sv)]
     n = len(sv)
@@ -814,7 +848,8 @@ def trackingVT_POS_updated(file, signal, track, cmn, solu, Acquired, cnslxyz, ep
             np.asarray(_struct_of(TckResult_Eph, p).absoluteSample).ravel()[k - 1]  # MATLAB's index check
     last = sv[-1]
     ms = int(_vec1(sbf.nav1, last) + _first(_struct_of(eph, last).sfb) * 20 + row)
-    ms = min(ms, np.asarray(_struct_of(TckResultCT, last).codeFreq).size)
+    if clamp:
+        ms = min(ms, np.asarray(_struct_of(TckResultCT, last).codeFreq).size)
     chans = []
     for p in sv:  # :109-132
         t = _struct_of(TckResultCT, p)
@@ -839,31 +874,14 @@ def trackingVT_POS_updated(file, signal, track, cmn, solu, Acquired, cnslxyz, ep
                                   _vec1(ns.clkBias, row), _vec1(ns.clkDrift, row), tt, C.byref(nav))
     if st != abi.OK:
         raise abi.GnssError(st, "gnss_vt_nav_init")
-    outs = (abi.GnssVtOut * (nsteps * n))()
+    outs = (OutT * (nsteps * n))()
     sols = (abi.GnssVtNavSol * nsteps)()
     f, keep = to_c_file(file)
     t, keep2 = to_c_track(track)
-    st = ctx.lib.gnss_tracking_vt(ctx.h, C.byref(f), C.byref(s), C.byref(t), n, nsteps, arr, C.byref(nav), outs,
-                                  sols)
+    st = getattr(ctx.lib, entry)(ctx.h, C.byref(f), C.byref(s), C.byref(t), n, nsteps, arr, C.byref(nav), outs, sols)
     ctx.check(st)
-    R = np.ctypeslib.as_array(outs).reshape(nsteps, n)  # a structured view of the records
-    entries = {}
-    for i, p in enumerate(sv):
-        e = SimpleNamespace(**{k: R[k][:, i].astype(np.float64) for k in VT_FIELDS})
-        e.sv_vel = R["sv_vel"][:, i].copy()
-        for k in ("amplitude", "navi_data", "navi_dataL035"):
-            setattr(e, k, np.zeros(nsteps))
-        entries[p] = e
-    nsol = _navsol_arrays(sols, nsteps, n)
-    TckResultVT = StructArray(entries)
-    if return_cn0:
-        rows = int(R["cn0_row"].max()) if nsteps else 0
-        cn0 = np.zeros((rows, n))
-        for i in range(n):
-            m = R["cn0_row"][:, i] > 0
-            cn0[R["cn0_row"][:, i][m] - 1, i] = R["CN0"][:, i][m]
-        return TckResultVT, nsol, cn0
-    return TckResultVT, nsol
+    R = np.ctypeslib.as_array(outs).reshape(nsteps, n).copy()  # the records as a structured array
+    return R, sols, sv, nsteps
 
 
 def _navsol_arrays(sols, nsteps, n):
@@ -883,3 +901,89 @@ def _navsol_arrays(sols, nsteps, n):
     out.R = S["R"][S["r_row"] > 0][:, :N].copy()
     out.record_correction = np.zeros((nsteps, n))  # correction(svindex) = 0 (:128, :469)
     return out
+
+
+# ---------------------------------------------------------------------------
+# trackingVT_POS_updated_multicorrelator.m: the 25-tap vector-tracking loop
+# ---------------------------------------------------------------------------
+def _mc_tap_fields(e, R, i):
+    """The 50 sums of channel i under the reference's names (E_i_060 ... L_q060, :401-450)."""
+    for k, name in enumerate(abi.MC_TAP_NAMES):
+        setattr(e, name.format("i"), R["tap_i"][:, i, k].copy())
+        setattr(e, name.format("q"), R["tap_q"][:, i, k].copy())
+
+
+def trackingVT_mc_run(file, signal, track, chans, codeFreq_series, pdi=1, *, ctx: Context | None = None):
+    """nsteps steps of trackingVT_POS_updated_multicorrelator.m's tracking half (:151-470) for
+    every channel, one launch of the 25-tap correlator per step (gnss_tracking_vt_mc_run):
+    codeFreq_series[s][i] = channel i's code frequency of step s (the caller's EKF prediction,
+    :209-214); `chans` (vt_channel states) advanced in place. Returns a dict of [nsteps][n]
+    arrays: the fields of trackingVT_run plus tap_i / tap_q [nsteps][n][25] in Spacing order
+    (0.6:-0.05:-0.6; E / P / L = taps 2 / 12 / 22). The records are in `GnssError.records` when a
+    channel stops (its status set)."""
+    ctx = ctx or default_context()
+    n = len(chans)
+    cf = np.ascontiguousarray(codeFreq_series, dtype=np.float64)
+    if cf.ndim != 2 or cf.shape[1] != n:
+        raise ValueError("codeFreq_series: [nsteps][n]")
+    nsteps = cf.shape[0]
+    arr = (abi.GnssVtChan * n)(*chans)
+    outs = (abi.GnssVtMcOut * (nsteps * n))()
+    f, keep = to_c_file(file)
+    s = to_c_signal(signal)
+    t, keep2 = to_c_track(track)
+    st = ctx.lib.gnss_tracking_vt_mc_run(ctx.h, C.byref(f), C.byref(s), C.byref(t), int(pdi), n, nsteps, arr,
+                                         cf.ctypes.data_as(C.POINTER(C.c_double)), outs)
+    for i in range(n):
+        C.memmove(C.byref(chans[i]), C.byref(arr[i]), C.sizeof(abi.GnssVtChan))
+    rec = np.ctypeslib.as_array(outs).reshape(nsteps, n)
+    out = {k: rec[k].copy() for k in rec.dtype.names}
+    try:
+        ctx.check(st)
+    except abi.GnssError as e:
+        e.records = out
+        raise
+    return out
+
+
+def trackingVT_mc_step(file, signal, track, chans, codeFreq_new, pdi=1, *, ctx: Context | None = None):
+    """One step of trackingVT_mc_run -> one dict per channel."""
+    cf = np.ascontiguousarray(codeFreq_new, dtype=np.float64).reshape(1, -1)
+    out = trackingVT_mc_run(file, signal, track, chans, cf, pdi, ctx=ctx)
+    return [{k: out[k][0, i] for k in out} for i in range(len(chans))]
+
+
+def trackingVT_POS_updated_multicorrelator(file, signal, track, cmn, solu, Acquired, cnslxyz, eph, sbf,
+                                           TckResult_Eph, TckResultCT, navSolutionsCT, *,
+                                           ctx: Context | None = None, ALPHA_=None, BETA_=None,
+                                           nsteps: int | None = None, return_cn0: bool = False):
+    """trackingVT_POS_updated_multicorrelator.m:1-609 -> (TckResultVT_mltCorr,
+    navSolutionsVT_mltCorr[, CN0_VT]): the vector-tracking loop SDR_main.m runs for
+    cmn.mltCorrON = [1 1] (gnss_tracking_vt_mc).
+
+    Arguments, initialisation and outputs as trackingVT_POS_updated, except what the reference's
+    file changes: 25 real replicas at Spacing = 0.6:-0.05:-0.6 correlated sample by sample
+    (E / P / L = Spacing(3) / (13) / (23), a real early-late codeError), the EKF's
+    prr_measured from carrFreq - signal.IF (:504), no msStartTckVT clamp (:97: an index past
+    TckResultCT raises IndexError as MATLAB does), and TckResultVT_mltCorr(prn) also carries the
+    50 tap sums under the reference's names (E_i_060 ... E_i_005, L_i005 ... L_i060 and the _q
+    twins, :401-450; tap_i / tap_q hold them as nsteps x 25 in Spacing order).
+    """
+    R, sols, sv, nsteps = _vt_loop(file, signal, track, cmn, solu, Acquired, cnslxyz, eph, sbf, TckResult_Eph,
+                                   TckResultCT, navSolutionsCT, ctx, ALPHA_, BETA_, nsteps, False,
+                                   "gnss_tracking_vt_mc", abi.GnssVtMcOut)
+    n = len(sv)
+    entries = {}
+    for i, p in enumerate(sv):
+        e = SimpleNamespace(**{k: R[k][:, i].astype(np.float64) for k in VT_FIELDS})
+        e.sv_vel = R["sv_vel"][:, i].copy()
+        e.tap_i, e.tap_q = R["tap_i"][:, i].copy(), R["tap_q"][:, i].copy()
+        _mc_tap_fields(e, R, i)
+        for k in ("amplitude", "navi_data", "navi_dataL035"):
+            setattr(e, k, np.zeros(nsteps))
+        entries[p] = e
+    nsol = _navsol_arrays(sols, nsteps, n)
+    res = StructArray(entries)
+    if return_cn0:
+        return res, nsol, _cn0_rows(R, nsteps, n)
+    return res, nsol

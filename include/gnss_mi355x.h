@@ -625,6 +625,78 @@ int gnss_tracking_vt(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *si
                      const gnss_track *track, int32_t n, int32_t nsteps, gnss_vt_chan *chans,
                      gnss_vt_nav *nav, gnss_vt_out *out, gnss_vt_navsol *sol);
 
+/* ---- trackingVT_POS_updated_multicorrelator.m: the 25-tap vector-tracking loop ------------
+ * Additive within ABI v13: new symbols and one new struct, no existing layout or meaning
+ * changes and gnss_abi_version() stays 13; a caller detects these entry points by symbol
+ * (dlsym / hasattr). Line cites below are of trackingVT_POS_updated_multicorrelator.m.
+ *
+ * The loop SDR_main.m runs for cmn.mltCorrON = [1 1]. It is trackingVT_POS_updated.m except:
+ * Spacing = 0.6:-0.05:-0.6 (:26), 25 taps, E / P / L = Spacing(3) / (13) / (23) = +0.5 / 0 /
+ * -0.5; every sample of every tap is despread against a real replica Code(ceil(t) + 2) of
+ * Code = [c(end) c(end-1) repmat(c,1,pdi) c(1) c(2)] (:104, :230-281; the pad's order is the
+ * reference's: ceil(t) = 0 reads c(end-1), -1 reads c(end)), so E / P / L are real sums and
+ * codeError a real early-late discriminator; remChip comes from the prompt colon (:354); the
+ * EKF measures prr with carrFreq - signal.IF (:504); and there is no msStartTckVT clamp.
+ * GNSS_EINDEX where MATLAB raises: a tap colon without exactly numSample elements, or a table
+ * index outside 1 .. 1023 * pdi + 4. Formats as gnss_tracking_vt_run. */
+#define GNSS_VT_MC_TAPS 25
+
+/* TckResultVT_mltCorr(prn).*(msIndex): gnss_vt_out's fields, then the 50 tap sums in Spacing
+ * order (E_i_060 .. E_i_005, P_i, L_i005 .. L_i060 and the _q twins, :401-450). E_i / P_i /
+ * L_i (and _q) equal taps 2 / 12 / 22. */
+typedef struct gnss_vt_mc_out {
+    double  E_i, E_q, P_i, P_q, L_i, L_q;
+    double  carrError, codeError, carrNco;
+    double  remChip, remCarrPhase, codeFreq, carrFreq;
+    int64_t numSample, absoluteSample;
+    double  codedelay;
+    double  CN0;
+    int32_t cn0_row;
+    int32_t status;
+    double  deltaPr;        /* written by gnss_tracking_vt_mc (0 from gnss_tracking_vt_mc_run) */
+    double  prRate;
+    double  sv_vel[3];
+    double  tap_i[GNSS_VT_MC_TAPS];
+    double  tap_q[GNSS_VT_MC_TAPS];
+} gnss_vt_mc_out;
+
+/* The tracking half (:151-470) with the caller's code frequency per step, one launch of the
+ * 25-tap correlator per step (csrc/vt_mc.hip): codeFreq_new[s * n + i], chans[] and out[s * n +
+ * i] as gnss_tracking_vt_run, n in 1..GNSS_VT_MAX_CH. The host sizes every read and clears it
+ * against the record before the launch: a channel whose step fails (GNSS_EINDEX; GNSS_EIO: read
+ * past EOF) stops there with out[..].status set and sits the later steps out (zero records);
+ * the call returns the first such status. GNSS_OPT_VT_BLOCKS sets the blocks per channel,
+ * GNSS_OPT_VT_SPAN the steps per staged IF window. */
+int gnss_tracking_vt_mc_run(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *signal,
+                            const gnss_track *track, int32_t pdi, int32_t n, int32_t nsteps,
+                            gnss_vt_chan *chans, const double *codeFreq_new, gnss_vt_mc_out *out);
+
+/* The whole loop (:151-609) with the EKF: nav as initialised by gnss_vt_nav_init, each step's
+ * code frequency from gnss_vt_nav_predict, the update with prr_measured = (carrFreq - IF) * c /
+ * Fc. Arguments and the stop at a channel error as gnss_tracking_vt. */
+int gnss_tracking_vt_mc(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *signal,
+                        const gnss_track *track, int32_t n, int32_t nsteps, gnss_vt_chan *chans,
+                        gnss_vt_nav *nav, gnss_vt_mc_out *out, gnss_vt_navsol *sol);
+
+/* The step's host half alone (no GPU). Prepare: *numSample = ceil(...) (:155) and each tap's
+ * colon ends -- element k of tap j is MATLAB's colon element of {tap_a[j], codeFreq_new / Fs,
+ * tap_c[j]} with numSample elements (tap_a / tap_c / numSample may be NULL) -- or GNSS_EINDEX. */
+int gnss_vt_mc_prepare(const gnss_signal *signal, int32_t pdi, const gnss_vt_chan *chan,
+                       double codeFreq_new, double tap_a[GNSS_VT_MC_TAPS],
+                       double tap_c[GNSS_VT_MC_TAPS], int64_t *numSample);
+
+/* ... and the scalar end (:354-391) from the step's 50 sums in Spacing order: the record and
+ * the advanced channel state. int8 I/Q byte offsets. */
+int gnss_vt_mc_nco_step(const gnss_signal *signal, const gnss_track *track, int32_t pdi,
+                        gnss_vt_chan *chan, double codeFreq_new,
+                        const double tap_i[GNSS_VT_MC_TAPS], const double tap_q[GNSS_VT_MC_TAPS],
+                        gnss_vt_mc_out *out);
+
+/* gnss_vt_nav_update with the 25-tap loop's measurement prr_measured = (carrFreq - IF) * c / Fc
+ * (:504); everything else is gnss_vt_nav_update's. */
+int gnss_vt_mc_nav_update(gnss_vt_nav *nav, const double *codeError, const double *codeFreq,
+                          const double *carrFreq, gnss_vt_navsol *sol);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
