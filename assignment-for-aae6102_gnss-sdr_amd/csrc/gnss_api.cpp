@@ -150,7 +150,29 @@ int fail(gnss_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
+// The sampling-rate floor of the tracking kernels (gnss_tracking_ct and its variants,
+// gnss_correlate_step): a lane correlates 8 samples at least and may hold one chip boundary
+// per tap, so 8 * codeFreq / Fs must stay below 1 for every code rate of the call -- the
+// nominal rate with 1 % for the DLL's excursions, and a caller-given code frequency where
+// there is one. The kernels flag a violating step with GNSS_EINDEX (d * M >= 1), which the
+// header keeps for indices MATLAB would reject; MATLAB runs such a rate, so the host
+// refuses it before any launch with GNSS_EARG. One predicate for every entry point: what it
+// admits, the kernels run.
+bool lane_rate_admitted(const gnss_signal* sg, double codeFreq_max)
+{
+    return sg->Fs > 0 && 8.0 * std::max(sg->codeFreqBasis * 1.01, codeFreq_max) / sg->Fs < 1.0;
+}
+
+int refuse_lane_rate(gnss_ctx* ctx, const gnss_signal* sg, double codeFreq_max)
+{
+    return fail(ctx, GNSS_EARG,
+                "Fs = %.9g Hz is below the sampling-rate floor of the tracking kernels: Fs must exceed "
+                "8 x the code rate (%.9g Hz with the 1 %% margin, i.e. Fs > %.9g Hz)",
+                sg->Fs, std::max(sg->codeFreqBasis * 1.01, codeFreq_max),
+                8.0 * std::max(sg->codeFreqBasis * 1.01, codeFreq_max));
+}
+
+#define HIP_TRY(expr)                                                                         \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \
         if (e_ != hipSuccess)                                                                  \
@@ -1334,8 +1356,7 @@ static int tracking_impl(gnss_ctx* ctx, const gnss_file* file, const gnss_signal
         if (pos->mc_pdi) return pos->mc_pdi == 1 ? pos->ctPOS : 0;
         return std::max<int64_t>(0, std::min<int64_t>(pos->ctPOS, (int64_t)N1 + pos->countinx[c]));
     };
-    if (8.0 * (sg->codeFreqBasis * 1.01) / sg->Fs >= 1.0)
-        return fail(ctx, GNSS_EARG, "Fs too low for the 8-sample lane groups (need Fs > 8.2 MHz)");
+    if (!lane_rate_admitted(sg, 0.0)) return refuse_lane_rate(ctx, sg, 0.0);
 
     // taps (trackingCT.m:24; ACF taps per trackingCT_multiCorr-GIVEN.m:25)
     TrkParams P{};
@@ -2044,6 +2065,7 @@ int gnss_correlate_step(gnss_ctx* ctx, const gnss_file* file, const gnss_signal*
     if (!ctx || !file || !sg || !taps || !sums_out || (n_taps != 3 && n_taps != 11) || prn < 1 || prn > 51)
         return GNSS_EARG;
     if (pdi != 1 && pdi != 10) return GNSS_EARG;
+    if (!lane_rate_admitted(sg, codeFreq)) return refuse_lane_rate(ctx, sg, codeFreq);
     HIP_TRY(hipSetDevice(ctx->device));
     const int64_t S = sg->Sample;
     TrkParams P{};

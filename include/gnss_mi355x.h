@@ -305,7 +305,14 @@ int gnss_acquisition(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *si
                      const gnss_acq *acq, gnss_acquired *out, gnss_acq_diag *diag);
 
 /* trackingCT.m replacement (trackingCT.m:1-530). The `countinx.mat` side file
- * (trackingCT.m:530) is the wrapper's job (MEX / Python mirror). */
+ * (trackingCT.m:530) is the wrapper's job (MEX / Python mirror).
+ * Sampling-rate floor (this call, its _pos / _mc / _multicorr variants and
+ * gnss_correlate_step): the correlator's lanes take 8 samples at least and hold at most one
+ * chip boundary per tap, so Fs must exceed 8 * 1.01 * codeFreqBasis (8.26584 MHz for the
+ * C/A code; gnss_correlate_step also 8 * its codeFreq argument). A lower rate is refused on
+ * the host, before any launch, with GNSS_EARG and a gnss_last_error text naming the floor
+ * (MATLAB runs such a rate, so it is no GNSS_EINDEX); the context stays usable. Every rate
+ * above the floor runs: no admitted rate ends in GNSS_EINDEX for its lane geometry. */
 int gnss_tracking_ct(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *signal,
                      const gnss_track *track, const gnss_acquired *acquired,
                      gnss_track_out *out);
