@@ -268,6 +268,8 @@ PROTOTYPES = {
                                       C.POINTER(C.c_double), C.POINTER(GnssVtMcOut)]),
     "gnss_vt_mc_nav_update": (C.c_int, [C.POINTER(GnssVtNav), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double), C.POINTER(GnssVtNavSol)]),
+    "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
+    "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libgnss_mi355x.so")
@@ -277,7 +279,7 @@ LOADED_PATH = None  # the library file the process bound (bench.py digests it)
 
 # gnss_ctx_set_option keys (include/gnss_mi355x.h, ABI v11)
 (OPT_FORCE_SUB, OPT_NO_PERSIST, OPT_FORCE_VPB, OPT_ACQ_ROCFFT, OPT_FINE_ROCFFT, OPT_ACQ_BATCH, OPT_ACQ_FUSED,
- OPT_ACQ_RING, OPT_ACQ_PIPE, OPT_VT_BLOCKS, OPT_FORCE_PEER, OPT_VT_SPAN) = range(12)
+ OPT_ACQ_RING, OPT_ACQ_PIPE, OPT_VT_BLOCKS, OPT_FORCE_PEER, OPT_VT_SPAN, OPT_SLOT_PATH) = range(13)
 MAX_DEVICES = 16
 
 

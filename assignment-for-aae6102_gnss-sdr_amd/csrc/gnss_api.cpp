@@ -57,6 +57,7 @@ struct gnss_ctx {
     int acq_fp64 = 1;      // acquisition correlation precision: 1 = fp64 (reference), 0 = fp32
     uint64_t window = 0;   // trackingCT: max IF bytes resident in HBM (0: the whole read range)
     int64_t opt[GNSS_OPT_COUNT] = {};  // gnss_ctx_set_option (test hooks; all 0 by default)
+    int lane_path = 0;                 // gnss_ctx_lane_path
     // multi-device context (gnss_ctx_create_multi): the member contexts (empty: a plain one);
     // the group itself is also a context on devices[0], for the entry points that do not shard
     std::vector<gnss_ctx*> members;
@@ -1023,6 +1024,8 @@ int gnss_ctx_set_option(gnss_ctx* ctx, int key, int64_t value)
     if (!ctx || key < 0 || key >= GNSS_OPT_COUNT) return GNSS_EARG;
     if (key == GNSS_OPT_VT_BLOCKS && (value < 0 || value > GNSS_VT_MAX_BLOCKS))
         return fail(ctx, GNSS_EARG, "GNSS_OPT_VT_BLOCKS outside 0..%d", GNSS_VT_MAX_BLOCKS);
+    if (key == GNSS_OPT_SLOT_PATH && (value < 0 || value > 2))
+        return fail(ctx, GNSS_EARG, "GNSS_OPT_SLOT_PATH outside 0..2");
     if (key == GNSS_OPT_VT_SPAN && (value < 0 || value > kVtSpan))
         return fail(ctx, GNSS_EARG, "GNSS_OPT_VT_SPAN outside 0..%d", kVtSpan);
     ctx->opt[key] = value;
@@ -1592,6 +1595,9 @@ static int tracking_impl(gnss_ctx* ctx, const gnss_file* file, const gnss_signal
     // (lane_correlate's capture queue): checked here for code rates up to cps_max, and a step
     // beyond that rate stops the channel with GNSS_EINDEX in the kernel (as d*M >= 1 does)
     P.qcap_dmax = cps_max;
+    // <= 3 taps: tap prefixes from the capture register wherever a lane holds at most
+    // kRegCapMax distinct boundary samples (lane_boundaries), else through the LDS slots
+    P.regcap = regcap_mask(P, cps_max, ctx->opt[GNSS_OPT_SLOT_PATH]);
     auto qcap_ok = [&](int sub) {
         return !GNSS_QCAP || P.ntaps <= 3 ||
                max_taps_in_lane(P.taps, P.tap_post, P.ntaps, 8 * sub, cps_max) <= kQcapMax;
@@ -1615,6 +1621,7 @@ static int tracking_impl(gnss_ctx* ctx, const gnss_file* file, const gnss_signal
     bool persist1 = vpb1 > 0, persist10 = vpb10 > 0;
     if (const char* pr = probe_env("GNSS_PROBE")) P.probe = atoi(pr);
     const int bpc1 = bpc_for(1, sub1), bpc10 = bpc_for(10, sub10);
+    ctx->lane_path = lane_regcap(P, sub1) && lane_regcap(P, sub10);
     if (bpc10 > kMaxBpc) return fail(ctx, GNSS_EARG, "Sample too large for the step geometry");
 
     // device state
@@ -2057,6 +2064,14 @@ int gnss_tracking_ct_mc(gnss_ctx* ctx, const gnss_file* file, const gnss_signal*
     return tracking_impl(ctx, file, sg, tr, acq, out, &pc);
 }
 
+int gnss_lane_boundaries(const double* taps, const double* post, int n_taps, int lane_samples, double cps_max)
+{
+    if (!taps || n_taps < 1 || n_taps > GNSS_MAX_TAPS || lane_samples < 1 || !(cps_max > 0.0)) return -1;
+    return lane_boundaries(taps, post, n_taps, lane_samples, cps_max);
+}
+
+int gnss_ctx_lane_path(const gnss_ctx* ctx) { return ctx ? ctx->lane_path : 0; }
+
 int gnss_correlate_step(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg, int prn, int pdi,
                         double remChip, double codeFreq, double carrierFreq, double remPhase,
                         int64_t pos_bytes, int n_taps, const double* taps, double* sums_out,
@@ -2106,6 +2121,8 @@ int gnss_correlate_step(gnss_ctx* ctx, const gnss_file* file, const gnss_signal*
     if (const int v = (int)ctx->opt[GNSS_OPT_FORCE_SUB]) {
         if (v >= 2 && v <= 4 && !P.exact_div && 8.0 * v * codeFreq / sg->Fs < 1.0) sub = v;
     }
+    P.regcap = regcap_mask(P, codeFreq / sg->Fs, ctx->opt[GNSS_OPT_SLOT_PATH]);
+    ctx->lane_path = lane_regcap(P, sub);
     const int bpc = (int)std::ceil(((S * pdi * 1.01 + 64) / 8.0 + 2) / ((double)kTrkThreads * sub));
     DevBuf d_chan, d_desc, d_ca, d_part, d_arrive, d_sums;
     HIP_TRY(d_chan.alloc(sizeof(TrkChan)));

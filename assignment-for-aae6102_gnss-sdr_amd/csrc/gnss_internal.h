@@ -304,6 +304,9 @@ struct TrkParams {
     int32_t given;
     // added to a tap's colon element before ceil (the +0.05 of trackingCT_POS_updated.m:216)
     double tap_post[GNSS_MAX_TAPS];
+    // <= 3 taps: bit `sub` set = the lanes of 8 * sub samples take their tap prefixes from the
+    // capture register (lane_regcap), clear = through the LDS slots
+    int32_t regcap;
 };
 
 // Samples per lane of the step kernel: 8 * SUB, SUB <= 4.
@@ -408,7 +411,8 @@ constexpr int run_bpc_cap(int ntaps) { return ntaps > 3 ? 192 : kMaxBpcRun; }
 constexpr int kMaxVpb = 16;      // virtual blocks per resident block of the persistent kernel
 // lane_correlate's capture queue (A/B knob): 0 = every tap's prefix read after every 8-sample
 // subgroup (the default: the queue measured 8-16 % slower at 11 taps and 8 % at 3,
-// profiles/r05_ab_cfg5_variants.txt); 1 = the queue above 3 taps; 2 = at 3 taps too
+// profiles/r05_ab_cfg5_variants.txt); 1 = the queue above 3 taps (<= 3 taps: register capture,
+// lane_boundaries below)
 #ifndef GNSS_QCAP
 #define GNSS_QCAP 0
 #endif
@@ -436,6 +440,56 @@ inline int max_taps_in_lane(const double* taps, const double* post, int n, int M
         best = c > best ? c : best;
     }
     return best;
+}
+// The most distinct boundary samples a lane of M samples can hold (gnss_lane_boundaries): taps
+// whose offsets differ by whole chips share a boundary and count once; the sets whose fractional
+// offsets fall in one window of the lane's (M - 1) dmax chips each bring a sample, plus one for
+// rounding (one more per set of two or more taps beyond the first: rounding can put each such
+// set's members a sample apart).
+inline int lane_boundaries(const double* taps, const double* post, int n, int M, double dmax)
+{
+    const double w = (M - 1) * dmax + 1e-9;
+    auto off = [&](int s) { return taps[s] + (post ? post[s] : 0.0); };
+    auto same = [&](int a, int b) {
+        const double f = off(a) - off(b), r = f - floor(f);
+        return r < 1e-9 || r > 1.0 - 1e-9;
+    };
+    int best = 0;
+    for (int a = 0; a < n; a++) {  // the window starting at tap a's boundary
+        int c = 0, multi = 0;
+        for (int b = 0; b < n; b++) {
+            bool first = true;  // b the first of its set
+            int size = 0;
+            for (int e = 0; e < n; e++) {
+                if (!same(b, e)) continue;
+                if (e < b) first = false;
+                size++;
+            }
+            if (!first) continue;
+            double f = off(b) - off(a);
+            f -= floor(f);
+            if (f < w || f > 1.0 - 1e-9) {
+                c++;
+                multi += size > 1;
+            }
+        }
+        c += multi > 1 ? multi : 1;
+        best = c > best ? c : best;
+    }
+    return best;
+}
+// lane_boundaries() up to which the <= 3-tap forms capture in registers: one boundary set and its
+// rounding allowance, what the one capture register pair holds without the rolled second pass
+constexpr int kRegCapMax = 2;
+// TrkParams.regcap: bit `sub` set = lanes of 8 * sub samples capture in registers
+inline bool lane_regcap(const TrkParams& p, int sub) { return p.ntaps <= 3 && ((p.regcap >> sub) & 1) != 0; }
+// force = GNSS_OPT_SLOT_PATH: 0 the rule above, 1 the slots everywhere, 2 the registers everywhere
+inline int regcap_mask(const TrkParams& p, double dmax, int64_t force)
+{
+    int m = 0;
+    for (int sub = 1; sub <= 4 && force != 1 && p.ntaps <= 3; sub++)
+        if (force == 2 || lane_boundaries(p.taps, p.tap_post, p.ntaps, 8 * sub, dmax) <= kRegCapMax) m |= 1 << sub;
+    return m;
 }
 // The persistent kernel's 16-B hand-off granules per channel. 3 taps: [2 (step parity)]
 // [kMaxBpcRun][6]. Above 3 taps only the loop's E/P/L go through the step's exchange

@@ -18,6 +18,10 @@
 // Reference: SDR_MATLAB-main/acqtckpos/trackingCT.m (citations inline).
 #include "gnss_internal.h"
 
+#include <cstddef>
+#include <type_traits>
+#include <utility>
+
 namespace gnss {
 
 namespace {
@@ -775,6 +779,23 @@ struct LdsRaw {
     const int4* p;  // this lane's group j at p[j * kTrkThreads]
     __device__ __forceinline__ int4 get(int j) const { return p[j * kTrkThreads]; }
 };
+typedef __attribute__((address_space(3))) const char lds_cchar;
+typedef __attribute__((address_space(3))) const double lds_cdbl;
+typedef double dbl2v __attribute__((ext_vector_type(2)));  // (a 16-B LDS read; double2 is a class on the host pass)
+typedef __attribute__((address_space(3))) const dbl2v lds_cdbl2;
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a
+// constant expression in the body (an asm immediate, if constexpr)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, I...>)
+{
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f)
+{
+    static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
 
 // Timing-probe builds only (tools/build_probe.sh, never the product library): bit 1 drops
 // the lane's sincos, bit 2 the per-tap boundary search, bit 4 the per-sample Wave / eta
@@ -812,16 +833,36 @@ __device__ __forceinline__ unsigned ca_bits_ext(unsigned cabits, int lane)
 #ifndef GNSS_SWP
 #define GNSS_SWP 0  // (lane_correlate: 1 / 2 = the next sample's Wave formed one sample ahead)
 #endif
-#ifndef GNSS_REGCAP
-#define GNSS_REGCAP 0  // (lane_correlate: 1 = tap prefixes captured in registers at 3 taps)
-#endif
 #ifndef GNSS_PHI_REG
 #define GNSS_PHI_REG 0  // (lane_correlate: 1 = the rotation basis phi[m] formed in registers)
 #endif
 #ifndef GNSS_TAPWIN
 #define GNSS_TAPWIN 1  // (A/B: 0 = per-tap colon element, scalar tap loads and two code shuffles)
 #endif
-template <int NT, int SUB, bool DIVIDE, bool RELOAD, int FMT, class Desc, class Raw>
+// Register capture (REGC, the <= 3-tap forms): one unrolled sample's hand-over. Lanes whose
+// capture sample is m copy the running sum into the capture register under the exec mask
+// (three VALU issues; a compare and two 64-bit selects are five), and the running sum, the
+// Wave base and the table address pass through the statement: the sums of sample m are final
+// before sample m + 1 accumulates, and no later sample's Wave or table read starts before
+// this point. Without those ties the scheduler loads the whole rotation table first and keeps
+// every sample's running sum live for a select chain at the end.
+template <int MS>
+__device__ __forceinline__ void capture_at(int capA, double& run_r, double& run_i, double& pre_r,
+                                           double& pre_i, double& kbt, unsigned& adr)
+{
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %[sv], exec\n\t"
+                 "v_cmpx_eq_u32_e32 vcc, %[m], %[cap]\n\t"
+                 "v_mov_b64 %[pr], %[rr]\n\t"
+                 "v_mov_b64 %[pi], %[ri]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [pr] "+v"(pre_r), [pi] "+v"(pre_i), [rr] "+v"(run_r), [ri] "+v"(run_i), [sv] "=&s"(sv),
+                   "+v"(kbt), "+v"(adr)
+                 : [cap] "v"(capA), [m] "n"(MS)
+                 : "vcc");
+}
+
+template <int NT, int SUB, bool DIVIDE, bool RELOAD, int FMT, bool REGC = false, class Desc, class Raw>
 __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* dp, const Raw& raw,
                                                int64_t ks, unsigned cabits, double2* myslot,
                                                const double2* zero, double (&oI)[NT], double (&oQ)[NT],
@@ -836,7 +877,9 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
     // the running sum is stored at the distinct interior capture samples only (queue entry =
     // the sample's rank among them), and each tap reads its one entry in the epilogue. The
     // value is the same running sum, so the same bits (pre = v + 0.0 either way).
-    constexpr bool QC = RELOAD && (GNSS_QCAP == 2 || (GNSS_QCAP && NT > 3));
+    constexpr bool QC = RELOAD && GNSS_QCAP && NT > 3;
+    static_assert(!REGC || (NT <= 3 && !QC && GNSS_CORR_PROBE == 0 && !GNSS_SWP && !GNSS_PHI_REG),
+                  "register capture: the <= 3-tap product forms");
     if constexpr ((GNSS_CORR_PROBE & 8) != 0) {  // (probe: no correlate at all)
 #pragma unroll
         for (int s = 0; s < NT; s++) { oI[s] = 0.0; oQ[s] = 0.0; }
@@ -1002,11 +1045,6 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
         mu_i = uni(dp->mu_i);
     }
 
-    // GNSS_REGCAP (3 taps, no capture queue): each tap's prefix is taken from the running sum in
-    // registers at its capture sample by a select, instead of through the LDS slots (a 16-B store
-    // per sample and a read per tap per subgroup): the correlate's only LDS traffic is then the
-    // rotation table's reads, which no store ahead of them delays. Same values, same bits.
-    constexpr bool RC = GNSS_REGCAP && !QC && NT <= 3;
     // GNSS_PHI_REG: the rotation basis phi[m] = m*dhi + m*dlo formed in registers (as
     // prepare_desc forms the table entry: the same operations, the same bits) instead of read
     double dhi_l = 0.0, dlo_l = 0.0;
@@ -1020,6 +1058,168 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
     // scheduler interleaves exactly those two chains. Same operations, same bits.
     double Wpipe = 0.0;
     if constexpr (GNSS_SWP) Wpipe = wave_at<DIVIDE>(kb + 1.0, f, phi0, Fs, rFs);
+    // REGC (<= 3 taps): no LDS slots. A tap's boundaries are a chip apart and taps a whole number
+    // of chips apart share theirs, so where the host's lane_boundaries() admits this form a lane
+    // has one interior capture sample, capA (the first tap's that has one), and its running sum is
+    // kept in one register pair (capture_at). A lane with a second one (E and L rounded a sample
+    // apart; a tap set with two boundaries in the span) is rare: its wave then takes the interior
+    // prefixes from a second, rolled pass of the same FMA chain. Either way a prefix is the
+    // running sum of that chain at the tap's capture sample: the same bits as through the slots.
+    if constexpr (REGC) {
+        constexpr unsigned kPhi = (unsigned)offsetof(StepDesc, phi), kRcs = (unsigned)offsetof(StepDesc, rcs);
+        int capA = -1;
+#pragma unroll
+        for (int s = NT - 1; s >= 0; s--) capA = (cap[s] >= 0 && cap[s] < M - 1) ? cap[s] : capA;
+        double preA_r = 0.0, preA_i = 0.0;
+        double kbt = kb;    // the Wave base and the descriptor's LDS address as capture_at hands them on
+        unsigned adr = 0u;
+        if constexpr (RELOAD) adr = (unsigned)(size_t)(lds_cchar*)dp;
+        // the rotation table's entry of sample m (RELOAD: from LDS at the address ta)
+        auto table = [&](const int m, const unsigned ta, double& phm, double2& rcs) __attribute__((always_inline)) {
+            if constexpr (RELOAD) {
+                phm = *(lds_cdbl*)(size_t)(ta + kPhi + 8u * (unsigned)m);
+                const dbl2v v = *(lds_cdbl2*)(size_t)(ta + kRcs + 16u * (unsigned)m);
+                rcs = make_double2(v.x, v.y);
+            } else {
+                phm = dp->phi[m];
+                rcs = ld_rcs(dp, m);
+            }
+        };
+        // the rotation (rc, rs) of sample m > 0: Wave from the base kbase (= kb; kb + m is exact,
+        // as kb + 8 j + mm is), the first-order residue folded into the table's entry
+        auto rotation = [&](const int m, const double kbase, const double phm, const double2 rcs, double& rc,
+                            double& rs) __attribute__((always_inline)) {
+            const double W = wave_at<DIVIDE>(kbase + (double)m, f, phi0, Fs, rFs);
+            const double eta = (W - Wb) - phm;
+            rc = __builtin_fma(-eta, rcs.y, rcs.x);
+            rs = __builtin_fma(eta, rcs.x, rcs.y);
+        };
+        auto accumulate = [&](const double rc, const double rs, const double xr, const double xi, double& rr,
+                              double& ri) __attribute__((always_inline)) {
+            rr = __builtin_fma(xr, rc, rr);
+            rr = __builtin_fma(-xi, rs, rr);
+            ri = __builtin_fma(xr, rs, ri);
+            ri = __builtin_fma(xi, rc, ri);
+        };
+        // The statements between two capture_at are scheduled on their own, so the pipeline is
+        // written out: beside sample m's four FMAs stand the rotation of sample m + 1 (an
+        // independent chain) and the table read of sample m + 2 (a sample of LDS latency cover).
+        double ph_n = 0.0, rc_n = 1.0, rs_n = 0.0;
+        double2 rcs_n = make_double2(1.0, 0.0);
+        table(1, adr, ph_n, rcs_n);
+        rotation(1, kbt, ph_n, rcs_n, rc_n, rs_n);
+        table(2, adr, ph_n, rcs_n);
+        static_for<SUB>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int NW = FMT == 1 ? 8 : 4;
+            unsigned wd[NW];
+            const bool part = lo > 8 * j || hi < 8 * j + 8;
+            if constexpr (FMT == 1) {
+                const int4 ra = raw.get(2 * j), rb = raw.get(2 * j + 1);
+                wd[0] = (unsigned)ra.x; wd[1] = (unsigned)ra.y; wd[2] = (unsigned)ra.z; wd[3] = (unsigned)ra.w;
+                wd[4] = (unsigned)rb.x; wd[5] = (unsigned)rb.y; wd[6] = (unsigned)rb.z; wd[7] = (unsigned)rb.w;
+            } else {
+                const int4 rj = raw.get(j);
+                wd[0] = (unsigned)rj.x; wd[1] = (unsigned)rj.y; wd[2] = (unsigned)rj.z; wd[3] = (unsigned)rj.w;
+                if (part) {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const int m0 = 8 * j + 2 * q;
+                        const unsigned k0 = (m0 >= lo && m0 < hi) ? 0x0000FFFFu : 0u;
+                        const unsigned k1 = (m0 + 1 >= lo && m0 + 1 < hi) ? 0xFFFF0000u : 0u;
+                        wd[q] &= k0 | k1;
+                    }
+                }
+            }
+            static_for<8>([&](auto mc) __attribute__((always_inline)) {
+                constexpr int mm = decltype(mc)::value, m = 8 * j + mm;
+                double xr, xi;
+                if constexpr (FMT == 1) {
+                    const unsigned word = wd[mm];
+                    xr = (double)(short)(word & 0xFFFFu) - mu_r;
+                    xi = (double)(short)(word >> 16) - mu_i;
+                    if (part && !(m >= lo && m < hi)) { xr = 0.0; xi = 0.0; }
+                } else {
+                    const unsigned word = wd[mm >> 1];
+                    constexpr int sh = (mm & 1) * 16;
+                    xr = (double)(int8_t)((word >> sh) & 0xFF);
+                    xi = (double)(int8_t)((word >> (sh + 8)) & 0xFF);
+                }
+                const double rc = rc_n, rs = rs_n;
+                if constexpr (m > 0 && m + 1 < M) {
+                    rotation(m + 1, kbt, ph_n, rcs_n, rc_n, rs_n);
+                    if constexpr (m + 2 < M) table(m + 2, adr, ph_n, rcs_n);
+                }
+                if constexpr (m > 0) {
+                    accumulate(rc, rs, xr, xi, run_r, run_i);
+                } else {  // (w = x exactly, as below)
+                    run_r += xr;
+                    run_i += xi;
+                }
+                if constexpr (m < M - 1) capture_at<m>(capA, run_r, run_i, preA_r, preA_i, kbt, adr);
+            });
+        });
+        bool more = false;
+#pragma unroll
+        for (int s = 0; s < NT; s++) {
+            const int cs = cap[s];
+            more = more || (cs >= 0 && cs < M - 1 && cs != capA);
+            pre_r[s] = (cs < 0 ? 0.0 : cs == M - 1 ? run_r : preA_r) + 0.0;
+            pre_i[s] = (cs < 0 ? 0.0 : cs == M - 1 ? run_i : preA_i) + 0.0;
+        }
+        if (__builtin_amdgcn_ballot_w64(more) != 0ull) {  // (rare, wave-uniform) the chain once more, rolled
+            double r2 = 0.0, i2 = 0.0;
+            double q_r[NT], q_i[NT];
+#pragma unroll
+            for (int s = 0; s < NT; s++) { q_r[s] = 0.0; q_i[s] = 0.0; }
+#pragma unroll
+            for (int j = 0; j < SUB; j++)  // (the groups by constant index: RegRaw stays in registers)
+#pragma unroll 1
+            for (int mm = 0; mm < (j == SUB - 1 ? 7 : 8); mm++) {
+                const int m = 8 * j + mm;
+                double xr, xi;
+                if constexpr (FMT == 1) {
+                    const int4 ga = raw.get(2 * j), gb = raw.get(2 * j + 1);
+                    const int c = mm & 3;
+                    const int wa = c == 0 ? ga.x : c == 1 ? ga.y : c == 2 ? ga.z : ga.w;
+                    const int wb = c == 0 ? gb.x : c == 1 ? gb.y : c == 2 ? gb.z : gb.w;
+                    const unsigned word = (unsigned)(mm < 4 ? wa : wb);
+                    xr = (double)(short)(word & 0xFFFFu) - mu_r;
+                    xi = (double)(short)(word >> 16) - mu_i;
+                } else {
+                    const int4 g = raw.get(j);
+                    const int c = mm >> 1, sh = (mm & 1) * 16;
+                    const unsigned word = (unsigned)(c == 0 ? g.x : c == 1 ? g.y : c == 2 ? g.z : g.w);
+                    xr = (double)(int8_t)((word >> sh) & 0xFF);
+                    xi = (double)(int8_t)((word >> (sh + 8)) & 0xFF);
+                }
+                if (!(m >= lo && m < hi)) { xr = 0.0; xi = 0.0; }
+                if (m > 0) {
+                    double ph;
+                    double2 rcs;
+                    table(m, adr, ph, rcs);
+                    double rc, rs;
+                    rotation(m, kb, ph, rcs, rc, rs);
+                    accumulate(rc, rs, xr, xi, r2, i2);
+                } else {
+                    r2 += xr;
+                    i2 += xi;
+                }
+#pragma unroll
+                for (int s = 0; s < NT; s++) {
+                    const bool at = cap[s] == m;
+                    q_r[s] = at ? r2 : q_r[s];
+                    q_i[s] = at ? i2 : q_i[s];
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NT; s++) {
+                const bool in = cap[s] >= 0 && cap[s] < M - 1;
+                pre_r[s] = in ? q_r[s] + 0.0 : pre_r[s];
+                pre_i[s] = in ? q_i[s] + 0.0 : pre_i[s];
+            }
+        }
+    }
     // one 8-sample subgroup: running sums into the LDS slots, tap prefixes captured
     auto subgroup = [&](const int j) {
         // fmt 0: 8 int8 I/Q pairs in one 16-B group; fmt 1: 8 int16 I/Q pairs in two
@@ -1095,19 +1295,12 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
             if constexpr (QC) {
                 if ((cmask >> m) & 1u)
                     myslot[__builtin_popcount(cmask & ((1u << m) - 1u)) * T] = make_double2(run_r, run_i);
-            } else if constexpr (RC) {
-#pragma unroll
-                for (int s = 0; s < NT; s++) {
-                    const bool at = cap[s] == m;
-                    pre_r[s] = at ? run_r : pre_r[s];
-                    pre_i[s] = at ? run_i : pre_i[s];
-                }
             } else {
                 myslot[mm * T] = make_double2(run_r, run_i);
             }
             if constexpr (GNSS_SWP == 2) __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (!QC && !RC) {
+        if constexpr (!QC) {
 #pragma unroll
             for (int s = 0; s < NT; s++) {
                 const unsigned idx = (unsigned)(cap[s] - 8 * j);
@@ -1120,7 +1313,9 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
 #ifndef GNSS_UNROLL_TAPS
 #define GNSS_UNROLL_TAPS 0  // (A/B: 1 = the > 3-tap subgroup loop unrolled like the 3-tap one)
 #endif
-    if constexpr (RELOAD && ((NT > 3 && !GNSS_UNROLL_TAPS) || (RC && GNSS_REGCAP == 2))) {
+    if constexpr (REGC) {
+        // (above)
+    } else if constexpr (RELOAD && NT > 3 && !GNSS_UNROLL_TAPS) {
         // descriptor in LDS: one subgroup at a time (unrolled, the compiler would keep
         // every subgroup's table values live)
 #pragma unroll 1
@@ -1423,7 +1618,7 @@ __device__ __forceinline__ double channel_sum(int bpc, int tid, Load load)
 // VGPRs. Grid: nch x bpc blocks; block b of a channel owns the 256*SUB consecutive
 // 8-sample groups starting at g_first + 256*SUB*b.
 // ---------------------------------------------------------------------------
-template <int NT, int SUB, bool DIVIDE, int FMT = 0>
+template <int NT, int SUB, bool DIVIDE, int FMT = 0, bool REGC = false>
 __global__ __launch_bounds__(kTrkThreads) void track_step_kernel(const TrkParams* __restrict__ pp,
                                                                 const TrkBuffers* __restrict__ bp, int bpc)
 {
@@ -1437,8 +1632,8 @@ __global__ __launch_bounds__(kTrkThreads) void track_step_kernel(const TrkParams
     const int blk = blockIdx.x - ch * bpc;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
-    // LDS: running sums slot[8][T], then the block reduction
-    constexpr int kSlot = 8 * T * 2;
+    // LDS: running sums slot[8][T] (none with register capture), then the block reduction
+    constexpr int kSlot = REGC ? 0 : 8 * T * 2;
     constexpr int kRed = red_words<red_taps<NT>()>();
     __shared__ __attribute__((aligned(16))) double s_mem[kSlot > kRed ? kSlot : kRed];
     __shared__ double s_fin[NV];
@@ -1483,7 +1678,7 @@ __global__ __launch_bounds__(kTrkThreads) void track_step_kernel(const TrkParams
     } else {
         if (tid == 0) s_zero = make_double2(0.0, 0.0);
         __syncthreads();
-        lane_correlate<NT, SUB, DIVIDE, false, FMT>(p, dp, RegRaw<SUB * GB>{raw}, 8 * g0 - dp->A, cabits,
+        lane_correlate<NT, SUB, DIVIDE, false, FMT, REGC>(p, dp, RegRaw<SUB * GB>{raw}, 8 * g0 - dp->A, cabits,
                                         reinterpret_cast<double2*>(s_mem) + tid, &s_zero, oI, oQ);
     }
 
@@ -1833,7 +2028,7 @@ __device__ __forceinline__ void prefetch_raw(const int8_t* iq, int64_t g0, int64
 #ifndef GNSS_WPE_TAPS
 #define GNSS_WPE_TAPS 2  // (A/B: waves per EU of the > 3-tap persistent forms; 3 = three blocks per CU)
 #endif
-template <int NT, int SUB, bool DIVIDE, bool VB = false>
+template <int NT, int SUB, bool DIVIDE, bool VB = false, bool REGC = false>
 __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT > 3 ? GNSS_WPE_TAPS : 3, NT > 3 ? GNSS_WPE_TAPS : 3))) void track_run_kernel(const TrkParams* __restrict__ pp,
                                                                const TrkBuffers* __restrict__ bp, int bpc,
                                                                int vpb, int nsteps, unsigned tag0)
@@ -1867,7 +2062,7 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const bool io = pblk == 0;
 
-    constexpr int kSlot = 8 * T * 2;                  // running sums [8][T] double2
+    constexpr int kSlot = REGC ? 0 : 8 * T * 2;       // running sums [8][T] double2 (register capture: none)
     constexpr int kRed = red_words<run_red_taps<NT>()>();  // block reduction
     constexpr int kPart = run_bpc_cap(NT) * NV;       // everyone's partials (as words)
     // Above 3 taps only E / P / L cross the step's exchange (kDefer, below); GNSS_DEFER 2 (one
@@ -2179,7 +2374,7 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
                 const int64_t g0 = uni(D.g_first) + ((int64_t)vb * T + tid) * SUB;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's global_load_lds landed
                 double oI[NT], oQ[NT];
-                lane_correlate<NT, SUB, DIVIDE, true, 0>(p, &D, LdsRaw{s_raw + tid}, 8 * g0 - A, cabits,
+                lane_correlate<NT, SUB, DIVIDE, true, 0, REGC>(p, &D, LdsRaw{s_raw + tid}, 8 * g0 - A, cabits,
                                                       reinterpret_cast<double2*>(s_mem) + tid, &s_zero, oI, oQ,
                                                       s_post);
                 __syncthreads();  // slots and s_raw free
@@ -2513,9 +2708,14 @@ hipError_t launch_track_step(const TrkParams& p, const TrkBuffers& b, const TrkD
                              hipStream_t s)
 {
     dim3 grid(p.nch * bpc), block(kTrkThreads);
+    const bool regc = lane_regcap(p, sub);
 #define GNSS_STEP(NT_, SUB_, DIV_, FMT_)                                                       \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && p.fmt == FMT_) {        \
-        hipLaunchKernelGGL((track_step_kernel<NT_, SUB_, DIV_, FMT_>), grid, block, 0, s, d.p, d.b, bpc); \
+        if (NT_ <= 3 && regc)                                                                  \
+            hipLaunchKernelGGL((track_step_kernel<NT_, SUB_, DIV_, FMT_, NT_ <= 3>), grid, block, 0, s, d.p, d.b, \
+                               bpc);                                                           \
+        else                                                                                   \
+            hipLaunchKernelGGL((track_step_kernel<NT_, SUB_, DIV_, FMT_>), grid, block, 0, s, d.p, d.b, bpc); \
         return hipGetLastError();                                                              \
     }
     GNSS_STEP(3, 1, false, 0) GNSS_STEP(3, 2, false, 0) GNSS_STEP(3, 3, false, 0) GNSS_STEP(3, 4, false, 0)
@@ -2535,16 +2735,25 @@ hipError_t launch_track_run(const TrkParams& p, const TrkBuffers& b, const TrkDe
 {
     if (vpb < 1 || bpc < 1) return hipErrorInvalidValue;
     dim3 grid(p.nch * ((bpc + vpb - 1) / vpb)), block(kTrkThreads);
+    const bool regc = lane_regcap(p, sub);
 #define GNSS_RUN(NT_, SUB_, DIV_)                                                              \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && vpb == 1) {            \
-        hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, false>), grid, block, 0, s, d.p, d.b, bpc, vpb, \
-                           nsteps, tag0);                                                      \
+        if (NT_ <= 3 && regc)                                                                  \
+            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, false, NT_ <= 3>), grid, block, 0, s, d.p, d.b, \
+                               bpc, vpb, nsteps, tag0);                                        \
+        else                                                                                   \
+            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, false>), grid, block, 0, s, d.p, d.b, bpc, \
+                               vpb, nsteps, tag0);                                             \
         return hipGetLastError();                                                              \
     }
 #define GNSS_RUNV(NT_, SUB_, DIV_)                                                             \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && vpb > 1) {             \
-        hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, true>), grid, block, 0, s, d.p, d.b, bpc, vpb, \
-                           nsteps, tag0);                                                      \
+        if (NT_ <= 3 && regc)                                                                  \
+            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, true, NT_ <= 3>), grid, block, 0, s, d.p, d.b, \
+                               bpc, vpb, nsteps, tag0);                                        \
+        else                                                                                   \
+            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, true>), grid, block, 0, s, d.p, d.b, bpc, \
+                               vpb, nsteps, tag0);                                             \
         return hipGetLastError();                                                              \
     }
     GNSS_RUN(3, 1, false) GNSS_RUN(3, 2, false) GNSS_RUN(3, 3, false) GNSS_RUN(3, 4, false)
@@ -2559,11 +2768,13 @@ hipError_t launch_track_run(const TrkParams& p, const TrkBuffers& b, const TrkDe
 int track_run_blocks_per_cu(const TrkParams& p, int sub, bool vb)
 {
     int nb = 0;
+    const bool regc = lane_regcap(p, sub);
 #define GNSS_OCC(NT_, SUB_, DIV_, VB_)                                                         \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && vb == VB_) {            \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(                                      \
-                &nb, reinterpret_cast<const void*>(track_run_kernel<NT_, SUB_, DIV_, VB_>),     \
-                kTrkThreads, 0) != hipSuccess)                                                 \
+        const void* fn = NT_ <= 3 && regc                                                      \
+                             ? reinterpret_cast<const void*>(track_run_kernel<NT_, SUB_, DIV_, VB_, NT_ <= 3>) \
+                             : reinterpret_cast<const void*>(track_run_kernel<NT_, SUB_, DIV_, VB_>); \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kTrkThreads, 0) != hipSuccess) \
             nb = 0;                                                                            \
         return nb;                                                                             \
     }

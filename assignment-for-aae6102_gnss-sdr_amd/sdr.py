@@ -118,6 +118,11 @@ class Context:
         """Test hook: force one engine path (abi.OPT_*, gnss_ctx_set_option)."""
         self.check(self.lib.gnss_ctx_set_option(self.h, int(key), int(value)))
 
+    def lane_path(self) -> int:
+        """1 when the last trackingCT / correlate_step took its tap prefixes from the capture
+        register for every lane span it used, 0 through the LDS slots (gnss_ctx_lane_path)."""
+        return int(self.lib.gnss_ctx_lane_path(self.h))
+
     def drop_record(self, dev=None):
         """Multi-device contexts: drop the members' resident copies of a device record (a
         DeviceRecord, a device pointer, or None for all), gnss_ctx_drop_record; needed only when

@@ -289,8 +289,27 @@ int  gnss_ctx_set_window(gnss_ctx *ctx, uint64_t bytes);
 #define GNSS_OPT_VT_SPAN      11 /* 1..2000 (ABI v13): steps per staged IF window of
                                     gnss_tracking_vt on a host record (2000; GNSS_EARG
                                     outside), so a short loop exercises the re-staging   */
-#define GNSS_OPT_COUNT        12
+#define GNSS_OPT_SLOT_PATH    12 /* the <= 3-tap correlators' tap prefixes, for tests and A/B:
+                                    1 = through the LDS running-sum slots (as above 3
+                                    taps) everywhere, 2 = from the capture register
+                                    everywhere (a lane with a second boundary then takes
+                                    the rolled second pass); 0 = by gnss_lane_boundaries  */
+#define GNSS_OPT_COUNT        13
 int  gnss_ctx_set_option(gnss_ctx *ctx, int key, int64_t value);
+/* The most distinct chip-boundary samples one correlator lane of `lane_samples` samples can hold
+ * for a tap set (`post` may be NULL) while the code advances at most `cps_max` chips per
+ * sample: taps a whole number of chips apart share their boundary and count once, plus one
+ * sample for rounding (one more per further set of two or more taps). The <= 3-tap correlators
+ * keep their tap prefixes in registers where this is at most 2, i.e. one boundary set per lane
+ * (E/P/L at 58 MHz, lanes up to 24 samples), else in the LDS slots. -1 for bad arguments.    */
+int  gnss_lane_boundaries(const double *taps, const double *post, int n_taps, int lane_samples,
+                          double cps_max);
+/* 1 when the context's last gnss_tracking / gnss_correlate_step ran the register-capture
+ * correlator for every lane span it used, 0 when any ran through the LDS slots. The choice is
+ * made when the call is planned: the value is meaningful on a single-device context after a
+ * call that returned GNSS_OK (a multi-device context's members plan their own calls; the
+ * group's value stays 0).                                                                   */
+int  gnss_ctx_lane_path(const gnss_ctx *ctx);
 
 /* Device memory owned by the ctx, for callers that keep an IF record resident
  * in HBM (gnss_file.dev_data) across calls. */

@@ -4,6 +4,13 @@ Args: out.json dir [dir ...] -- ksub [ksub ...]"""
 import csv, glob, json, sys
 import numpy as np
 
+
+def named(k, name):
+    """k in name; a pattern that closes its template list ("...false>") also names the kernel's
+    forms with further template arguments after those ("...false, true>")."""
+    return k in name or (k.endswith(">") and k[:-1] + "," in name)
+
+
 args = sys.argv[1:]
 out_path, rest = args[0], args[1:]
 cut = rest.index("--")
@@ -14,7 +21,7 @@ for k in ksubs:
     for d in dirs:
         for p in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
             for r in csv.DictReader(open(p)):
-                if k not in r.get("Kernel_Name", ""):
+                if not named(k, r.get("Kernel_Name", "")):
                     continue
                 key = (p, r.get("Dispatch_Id", r.get("Correlation_Id")))
                 c = r.get("Counter_Name")
@@ -26,7 +33,7 @@ for k in ksubs:
     for d in dirs:
         for p in glob.glob(d + "/**/*kernel_trace.csv", recursive=True):
             for r in csv.DictReader(open(p)):
-                if k in r.get("Kernel_Name", ""):
+                if named(k, r.get("Kernel_Name", "")):
                     durs.append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     if durs:
         res[k]["duration_us"] = {"median_per_dispatch": float(np.median(durs)), "dispatches": len(durs)}

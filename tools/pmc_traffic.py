@@ -6,11 +6,17 @@ import csv, glob, json, sys
 import numpy as np
 
 
+def named(k, name):
+    """k in name; a pattern that closes its template list ("...false>") also names the kernel's
+    forms with further template arguments after those ("...false, true>")."""
+    return k in name or (k.endswith(">") and k[:-1] + "," in name)
+
+
 def per_dispatch(d, counter, ksub):
     vals = {}
     for p in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(p)):
-            if ksub in r.get("Kernel_Name", "") and r.get("Counter_Name") == counter:
+            if named(ksub, r.get("Kernel_Name", "")) and r.get("Counter_Name") == counter:
                 key = r.get("Dispatch_Id", r.get("Correlation_Id"))
                 vals[key] = vals.get(key, 0.0) + float(r["Counter_Value"])
     return np.array(list(vals.values()))

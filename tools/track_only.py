@@ -25,6 +25,11 @@ track.msToProcessCT_1ms, track.msToProcessCT_10ms = N1, N10
 taps = None if ntaps == 3 else np.array([-0.5, -0.4, -0.3, -0.2, -0.1, 0.0, 0.1, 0.2, 0.3, 0.4, 0.5])
 if os.environ.get("TRK_SUB"):  # lane span 8 * v samples (GNSS_OPT_FORCE_SUB; A/B of the lane geometry)
     ctx.set_option(pkg.abi.OPT_FORCE_SUB, int(os.environ["TRK_SUB"]))
+if os.environ.get("TRK_SLOT"):  # GNSS_OPT_SLOT_PATH: 1 = the <= 3-tap prefixes through the LDS slots, 2 = registers
+    ctx.set_option(pkg.abi.OPT_SLOT_PATH, int(os.environ["TRK_SLOT"]))
+if os.environ.get("TRK_SPACING"):  # E/P/L at +- this many chips (track.CorrelatorSpacing and the taps)
+    track.CorrelatorSpacing = float(os.environ["TRK_SPACING"])
+    taps = np.array([-track.CorrelatorSpacing, 0.0, track.CorrelatorSpacing])
 if os.environ.get("TRK_PROFILE"):
     ctx.set_profiling(True)  # per-launch hipEvents: track10_kernel_ms = the 10-ms launch(es)
 for it in range(int(os.environ.get('TRK_ITERS', '2'))):
