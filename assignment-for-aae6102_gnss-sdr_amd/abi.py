@@ -171,6 +171,35 @@ class GnssVtNavSol(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+# the positioning half of trackingCT_POS_updated.m (gnss_ct_pos_solve; additive within ABI v13)
+ENOCONV = 6
+CT_POS_UPDATED, CT_POS_MULTICORR = 0, 1
+# navSolutionsCT's fields (trackingCT_POS_updated.m:509-551) and their values per row (0: n)
+NAVSOL_CT_FIELDS = [("rawPseudorange", 0), ("usrPos", 3), ("usrVel", 3), ("usrPosENU", 3), ("usrPosLLH", 3),
+                    ("clkBias", 1), ("usrVelENU", 3), ("clkDrift", 1), ("DOP", 4), ("satEA", 0), ("satAZ", 0),
+                    ("timeTransmit", 0), ("codePhaseMeas", 0), ("localTime", 1)]
+
+
+class GnssCtPosCfg(C.Structure):
+    _fields_ = [("n", C.c_int32), ("mode", C.c_int32), ("dataType", C.c_int32), ("msToProcessCT_1ms", C.c_int32),
+                ("pdi", C.c_int32), ("reserved", C.c_int32), ("navSolPeriod", C.c_double), ("Fs", C.c_double),
+                ("IF", C.c_double), ("codelength", C.c_double), ("ms", C.c_double), ("cSpeed", C.c_double),
+                ("doy", C.c_double), ("cnslxyz", C.c_double * 3), ("ALPHA", C.c_double * 4),
+                ("BETA", C.c_double * 4), ("countinx", C.c_int32 * VT_MAX_CH), ("nav1", C.c_int64 * VT_MAX_CH),
+                ("sfb1", C.c_int64 * VT_MAX_CH), ("sampleStart", C.c_int64 * VT_MAX_CH),
+                ("TOW1", C.c_double * VT_MAX_CH), ("eph", GnssEphSv * VT_MAX_CH)]
+
+
+class GnssNavSolCt(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("rows", C.c_int64)] + \
+               [(f, C.POINTER(C.c_double)) for f, _ in NAVSOL_CT_FIELDS] + \
+               [("Index", C.POINTER(C.c_int64)), ("index", C.POINTER(C.c_int64)),
+                ("carrFreqMeas", C.POINTER(C.c_double)), ("iters", C.POINTER(C.c_int32))]
+
+
+ADDED_STRUCTS.update({"gnss_ct_pos_cfg": "GnssCtPosCfg", "gnss_nav_sol_ct": "GnssNavSolCt"})
+
+
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
                 ("carr_phase0", C.c_double), ("cn0_dbhz", C.c_double), ("bit_seed", C.c_uint64),
@@ -268,6 +297,9 @@ PROTOTYPES = {
                                       C.POINTER(C.c_double), C.POINTER(GnssVtMcOut)]),
     "gnss_vt_mc_nav_update": (C.c_int, [C.POINTER(GnssVtNav), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double), C.POINTER(GnssVtNavSol)]),
+    # trackingCT_POS_updated.m's positioning half (additive within ABI v13: detected by symbol)
+    "gnss_ct_pos_solve": (C.c_int, [C.c_void_p, C.POINTER(GnssCtPosCfg), C.POINTER(GnssTrackOut),
+                                    C.POINTER(GnssNavSolCt)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

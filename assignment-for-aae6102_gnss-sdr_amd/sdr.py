@@ -6,6 +6,9 @@
                                                                    trackingCT.m:1
     [TckResultCT_pos, CN0_CT] = trackingCT_POS(file, signal, track, Acquired, countinx)
                                    tracking loop of trackingCT_POS_updated.m:1-413
+    [TckResultCT_pos, navSolutionsCT] = trackingCT_POS_updated(file, signal, track, cmn, Acquired,
+                                   TckResult_Eph, cnslxyz, eph, sbf, solu, countinx=countinx)
+                                   the whole of trackingCT_POS_updated.m, positioning included
     [ephemeris, ALLTckResult, for_prest] = naviDecode_updated(Acquired, ALLTckResult)
                                                                    naviDecode_updated.m:1
 
@@ -471,7 +474,7 @@ def trackingCT_POS(file, signal, track, Acquired, countinx, *, ctx: Context | No
     The reference reads `countinx` from countinx.mat (:29) and indexes it by the channel's
     position in Acquired (quirk A.17); pass that vector here. track.ctPOS is the step count
     (datalength, :50). The positioning half of the reference function (pseudoranges,
-    least squares, :420-565) is out of scope: TckResultCT_pos carries the fields of
+    least squares, :420-565) is ct_positioning / trackingCT_POS_updated: TckResultCT_pos carries the fields of
     :273-292 (E_i ... delayValue, absoluteSampleCodedelay) per PRN, one row per step.
     """
     ctx = ctx or default_context()
@@ -514,7 +517,8 @@ def trackingCT_POS_updated_multicorrelator(file, signal, track, Acquired, *,
     track.msPosCT (datalength, :49; initParameters.m does not define it, the caller sets
     it) and track.pdi (:46, 1 or 10) give msPosCT/pdi steps, every one at that pdi. The 25
     taps at Spacing = 0.6:-0.05:-0.6 are all recorded; E/P/L = Spacing(3)/(13)/(23) drive
-    the loops. The positioning half (:446-590) is out of scope.
+    the loops. The positioning half (:446-590) is ct_positioning(..., mode="multicorr") on
+    the returned records.
     """
     ctx = ctx or default_context()
     nsv = len(Acquired.sv)
@@ -992,3 +996,175 @@ def trackingVT_POS_updated_multicorrelator(file, signal, track, cmn, solu, Acqui
     if return_cn0:
         return res, nsol, _cn0_rows(R, nsteps, n)
     return res, nsol
+
+
+# ---------------------------------------------------------------------------
+# findPosSV.m and the positioning half of trackingCT_POS_updated.m: navSolutionsCT
+# ---------------------------------------------------------------------------
+def findPosSV(file, Acquired, eph):
+    """findPosSV.m:17-38 -> nAcquired: Acquired's channels whose ephemeris(prn).updateflag is 1,
+    in Acquired's order (SDR_main.m:59,76 then loads it back as nAcquired). The reference's
+    return value is the PRN list, which is nAcquired.sv; its side file
+    nAcquired_<fileName>_<skip>.mat (:42) is not written."""
+    keep = [i for i, p in enumerate(np.atleast_1d(Acquired.sv))
+            if int(getattr(_struct_of(eph, p), "updateflag", 0)) == 1]
+    print("Satellites used for positioning: ")
+    print(" ".join(f"{int(np.atleast_1d(Acquired.sv)[i]):02d}" for i in keep) + " \n")
+    pick = lambda v, dt: np.array([np.atleast_1d(v)[i] for i in keep], dtype=dt)
+    return SimpleNamespace(sv=pick(Acquired.sv, np.int64), SNR=pick(Acquired.SNR, np.float64),
+                           Doppler=pick(Acquired.Doppler, np.float64), codedelay=pick(Acquired.codedelay, np.int64),
+                           fineFreq=pick(Acquired.fineFreq, np.float64))
+
+
+class NavSolCtBuffers:
+    """Caller-allocated gnss_nav_sol_ct: `cap` rows of every navSolutionsCT field for n channels."""
+
+    def __init__(self, n: int, cap: int):
+        self.n, self.cap = int(n), max(int(cap), 1)
+        o = abi.GnssNavSolCt()
+        o.cap = self.cap
+        self.arr = {}
+        for f, w in abi.NAVSOL_CT_FIELDS:
+            self.arr[f] = np.zeros((self.cap, w or self.n))
+            setattr(o, f, self.arr[f].ctypes.data_as(C.POINTER(C.c_double)))
+        self.arr["Index"] = np.zeros(self.cap, dtype=np.int64)
+        self.arr["index"] = np.zeros((self.cap, self.n), dtype=np.int64)
+        self.arr["carrFreqMeas"] = np.zeros((self.cap, self.n))
+        self.arr["iters"] = np.zeros(self.cap, dtype=np.int32)
+        o.Index = self.arr["Index"].ctypes.data_as(C.POINTER(C.c_int64))
+        o.index = self.arr["index"].ctypes.data_as(C.POINTER(C.c_int64))
+        o.carrFreqMeas = self.arr["carrFreqMeas"].ctypes.data_as(C.POINTER(C.c_double))
+        o.iters = self.arr["iters"].ctypes.data_as(C.POINTER(C.c_int32))
+        self.c = o
+
+    def result(self) -> SimpleNamespace:
+        """navSolutionsCT (trackingCT_POS_updated.m:509-551): rows x n / 3 / 4 matrices, clkBias /
+        clkDrift / localTime as vectors; plus Index (the tracking step of each row), index,
+        carrFreqMeas and iters, which the reference's struct does not have."""
+        rows = int(self.c.rows)
+        out = SimpleNamespace()
+        for f, w in abi.NAVSOL_CT_FIELDS:
+            a = self.arr[f][:rows].copy()
+            setattr(out, f, a[:, 0] if w == 1 else a)
+        for f in ("Index", "index", "carrFreqMeas", "iters"):
+            setattr(out, f, self.arr[f][:rows].copy())
+        return out
+
+
+def _ct_pos_cfg(file, signal, track, cmn, Acquired, cnslxyz, eph, sbf, solu, countinx, TckResult_Eph, sampleStartMea,
+                mode, ALPHA_, BETA_):
+    sv = [int(p) for p in np.atleast_1d(Acquired.sv)]
+    n = len(sv)
+    if n > abi.VT_MAX_CH:
+        raise ValueError(f"positioning takes at most {abi.VT_MAX_CH} channels")
+    modes = {"pos_updated": abi.CT_POS_UPDATED, "multicorr": abi.CT_POS_MULTICORR}
+    if mode not in modes:
+        raise ValueError("mode is 'pos_updated' or 'multicorr'")
+    cfg = abi.GnssCtPosCfg()
+    cfg.n, cfg.mode, cfg.dataType = n, modes[mode], int(file.dataType)
+    cfg.msToProcessCT_1ms = int(track.msToProcessCT_1ms)
+    cfg.pdi = int(getattr(track, "pdi", 1))
+    cfg.navSolPeriod = float(solu.navSolPeriod)
+    cfg.Fs, cfg.IF, cfg.codelength, cfg.ms = float(signal.Fs), float(signal.IF), float(signal.codelength), float(signal.ms)
+    cfg.cSpeed, cfg.doy = float(cmn.cSpeed), float(cmn.doy)
+    cfg.cnslxyz[:] = [float(x) for x in np.asarray(cnslxyz, dtype=np.float64).ravel()[:3]]
+    cfg.ALPHA[:] = [float(x) for x in (ALPHA_ if ALPHA_ is not None else ALPHA)]
+    cfg.BETA[:] = [float(x) for x in (BETA_ if BETA_ is not None else BETA)]
+    cx = np.asarray(countinx).reshape(-1)
+    for i, p in enumerate(sv):
+        e = _struct_of(eph, p)
+        cfg.countinx[i] = int(cx[i])  # by channel position (:29,183; quirk A.17)
+        cfg.nav1[i] = int(_vec1(sbf.nav1, p))
+        cfg.sfb1[i] = int(_first(e.sfb))
+        cfg.TOW1[i] = _first(e.TOW)
+        cfg.eph[i] = eph_sv(eph, p)
+        if sampleStartMea is not None:  # max(sampleStart) + 1 given outright (:160)
+            cfg.sampleStart[i] = int(sampleStartMea) - 1
+        else:  # :156 (MATLAB's 1-based index; raises as MATLAB does past the end)
+            k = cfg.nav1[i] + cfg.sfb1[i] * 20
+            a = np.asarray(_struct_of(TckResult_Eph, p).absoluteSample).ravel()
+            if k < 1:
+                raise IndexError("TckResult_Eph(prn).absoluteSample(nav1 + sfb(1)*20): index below 1")
+            cfg.sampleStart[i] = int(a[k - 1])
+    return cfg, sv
+
+
+def ct_positioning(TckResultCT, file, signal, track, cmn, Acquired, cnslxyz, eph, sbf, solu, *, countinx,
+                   TckResult_Eph=None, sampleStartMea: int | None = None, mode: str = "pos_updated",
+                   ctx: Context | None = None, ALPHA_=None, BETA_=None):
+    """The positioning half of trackingCT_POS_updated.m (:147-171, :420-565; mode="pos_updated")
+    or of trackingCT_POS_updated_multicorrelator.m (:446-590; mode="multicorr", track.pdi) as a
+    pass over given tracking records -> navSolutionsCT (gnss_ct_pos_solve).
+
+    TckResultCT is the StructArray of trackingCT_POS / trackingCT_POS_updated_multicorrelator (or
+    any per-PRN structs with absoluteSample, remChip, codeFreq, carrFreq), or their raw
+    TrackOutBuffers; DeviceTrackOutBuffers keep the records in HBM and only the measurement
+    table crosses PCIe. sampleStartMea replaces TckResult_Eph (:156-160) when given. Host records
+    need no GPU (ctx may stay None without one). MATLAB's errors -> GnssError (index = 0:
+    EINDEX; fewer than 4 satellites: EARG); olspos.m's uncapped loop stops with ENOCONV.
+    """
+    if sampleStartMea is None and TckResult_Eph is None:
+        raise ValueError("ct_positioning needs TckResult_Eph or sampleStartMea")
+    cfg, sv = _ct_pos_cfg(file, signal, track, cmn, Acquired, cnslxyz, eph, sbf, solu, countinx, TckResult_Eph,
+                          sampleStartMea, mode, ALPHA_, BETA_)
+    n = len(sv)
+    lib = abi.load()
+    if isinstance(TckResultCT, TrackOutBuffers):
+        rec = TckResultCT.c
+        steps = int(TckResultCT.len[:n].min()) if n else 0
+        if isinstance(TckResultCT, DeviceTrackOutBuffers):
+            ctx = ctx or default_context()
+            TckResultCT.sync_producer()
+    else:
+        series = [[np.asarray(getattr(_struct_of(TckResultCT, p), f), dtype=np.float64).ravel()
+                   for f in ("absoluteSample", "remChip", "codeFreq", "carrFreq")] for p in sv]
+        lens = np.array([min(len(x) for x in s) for s in series], dtype=np.int64)
+        steps = int(lens.min()) if n else 0
+        arr = np.zeros((n, abi.NFIELDS, max(int(lens.max()) if n else 1, 1)))
+        for i, s in enumerate(series):
+            for f, x in zip(("absoluteSample", "remChip", "codeFreq", "carrFreq"), s):
+                arr[i, abi.FIELDS_POS.index(f), : lens[i]] = x[: lens[i]]
+        rec = abi.GnssTrackOut()
+        rec.max_len = arr.shape[2]
+        rec.rec = arr.ctypes.data_as(C.POINTER(C.c_double))
+        rec.len = lens.ctypes.data_as(C.POINTER(C.c_int64))
+    buf = NavSolCtBuffers(n, steps)
+    h = ctx.h if ctx is not None else None
+    st = lib.gnss_ct_pos_solve(h, C.byref(cfg), C.byref(rec), C.byref(buf.c))
+    if st != abi.OK:
+        msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
+        raise abi.GnssError(st, msg)
+    return buf.result()
+
+
+def trackingCT_POS_updated(file, signal, track, cmn, Acquired, TckResult_Eph, cnslxyz, eph, sbf, solu, *, countinx,
+                           ctx: Context | None = None, device_records: bool = False, ALPHA_=None, BETA_=None):
+    """trackingCT_POS_updated.m:1-573 -> (TckResultCT_pos, navSolutionsCT): the reference's
+    signature plus the `countinx` it loads from countinx.mat (:29).
+
+    The scalar loops run as in trackingCT_POS (gnss_tracking_ct_pos, track.ctPOS steps), then the
+    positioning pass over their records (gnss_ct_pos_solve; positioning does not feed back into
+    the loops). With device_records the records stay in HBM between the two calls and the
+    measurement table alone crosses PCIe before TckResultCT_pos is downloaded for the return
+    value. navSolutionsCT is what trackingVT_POS_updated takes. The side files of :573-574 are
+    not written.
+    """
+    ctx = ctx or default_context()
+    nsv = len(Acquired.sv)
+    f, k1 = to_c_file(file)
+    s = to_c_signal(signal)
+    t, k2 = to_c_track(track, None, None)
+    a = to_c_acquired(Acquired)
+    cx = np.ascontiguousarray(np.asarray(countinx).reshape(-1)[:nsv], dtype=np.int32)
+    ctPOS = int(track.ctPOS)
+    if device_records:
+        buf = DeviceTrackOutBuffers(nsv, track, 0, device=f"cuda:{ctx.device}", ctPOS=ctPOS)
+        buf.sync_producer()
+    else:
+        buf = TrackOutBuffers(nsv, track, 0, ctPOS=ctPOS)
+    ctx.check(ctx.lib.gnss_tracking_ct_pos(ctx.h, C.byref(f), C.byref(s), C.byref(t), C.byref(a), ctPOS,
+                                           cx.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(buf.c)))
+    nav = ct_positioning(buf, file, signal, track, cmn, Acquired, cnslxyz, eph, sbf, solu, countinx=cx,
+                         TckResult_Eph=TckResult_Eph, ctx=ctx, ALPHA_=ALPHA_, BETA_=BETA_)
+    hb = buf.host() if device_records else buf
+    return build_tck_result(Acquired, hb, None, abi.FIELDS_POS), nav

@@ -1,8 +1,10 @@
-"""SDR_main.m (SDR_MATLAB-main/SDR_main.m:16-56) on the MI355X engine: parameter
+"""SDR_main.m (SDR_MATLAB-main/SDR_main.m:16-70) on the MI355X engine: parameter
 initialisation, acquisition, conventional tracking and navigation-data decoding, with the
 reference's result files (Acquired_<file>_<skip>.mat, TckResult_Eph<file>_<s>.mat,
-eph_<file>_<s>.mat, sbf_<file>_<s>.mat) written and re-used the same way. Positioning
-(SDR_main.m:59-) is outside this engine.
+eph_<file>_<s>.mat, sbf_<file>_<s>.mat) written and re-used the same way; then the satellites
+usable for positioning (findPosSV, :65) and scalar tracking with positioning
+(trackingCT_POS_updated), whose navSolutionsCT is what the vector-tracking loops start from
+(:73-99).
 
     python examples/sdr_main.py --file Opensky.bin          # a recorded IF file
     python examples/sdr_main.py --synthetic --n10 45000     # the synthetic Opensky scenario
@@ -102,6 +104,33 @@ def main():
         e = eph(p)
         print(f"PRN {p:2d}: nav1 {sbf.nav1[p - 1]}, subframes decoded {len(e.sfb)}, "
               f"updateflag {e.updateflag}" + (f", sqrta {e.sqrta[0]:.6f}" if len(e.sqrta) else ""))
+
+    # Satellites usable for positioning, then scalar tracking and positioning (SDR_main.m:64-70)
+    nAcquired = sdr.findPosSV(file, Acquired, eph)
+    if len(nAcquired.sv) < 4:
+        print("Fewer than 4 satellites with a decoded ephemeris: no positioning. \n")
+        return
+    print("Positioning ...\n")
+    lib = sdr.abi.load()
+    cnslxyz = (sdr.abi.C.c_double * 3)()
+    lib.gnss_geo(sdr.abi.GEO_LLH2XYZ, (sdr.abi.C.c_double * 3)(*solu.iniPos), cnslxyz)  # llh2xyz(solu.iniPos)
+    # countinx as trackingCT saved it (countinx.mat): the reference reads it by the channel's
+    # POSITION in nAcquired, not by PRN (trackingCT_POS_updated.m:29,183)
+    try:
+        TckResultCT_pos, navSolutionsCT = sdr.trackingCT_POS_updated(
+            file, signal, track, cmn, nAcquired, TckResultCT, list(cnslxyz), eph, sbf, solu, countinx=countinx,
+            ctx=ctx, device_records=True)
+    except sdr.abi.GnssError as e:
+        # (the synthetic scenario's SVs all broadcast one ephemeris, csrc/lnav.cpp: their geometry
+        # is singular and the fit cannot converge; a recorded IF file gives a fix)
+        print("Positioning stopped where MATLAB would raise or spin:", e)
+        return
+    rows = len(navSolutionsCT.localTime)
+    print(f"navSolutionsCT: {rows} epochs")
+    if rows:
+        e, n, u = navSolutionsCT.usrPosENU[-1]
+        print(f"last fix: E = {e:.3f} N = {n:.3f} U = {u:.3f} m, clkBias {navSolutionsCT.clkBias[-1]:.3f} m, "
+              f"localTime {navSolutionsCT.localTime[-1]:.6f}")
 
 
 if __name__ == "__main__":

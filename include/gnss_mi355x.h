@@ -337,7 +337,7 @@ int gnss_tracking_ct(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *si
                      gnss_track_out *out);
 
 /* The tracking loop of trackingCT_POS_updated.m (its positioning half,
- * :420-565, is out of scope). Replaces the per-channel correlator / NCO / DLL / PLL of
+ * :420-565, is gnss_ct_pos_solve, a pass over this call's records). Replaces the per-channel correlator / NCO / DLL / PLL of
  * trackingCT_POS_updated.m:92-144,179-413:
  *   - file_ptr = (Sample - codedelay + 1 + skip*Sample)*bytes (:108-110), one continuous
  *     read per channel (no re-seek at the 1 -> 10 ms switch);
@@ -359,7 +359,8 @@ int gnss_tracking_ct_pos(gnss_ctx *ctx, const gnss_file *file, const gnss_signal
                          const int32_t *countinx, gnss_track_out *out);
 
 /* The tracking loop of trackingCT_POS_updated_multicorrelator.m (the
- * 25-tap sibling; its positioning half, :446-590, is out of scope). Replaces the channel
+ * 25-tap sibling; its positioning half, :446-590, is gnss_ct_pos_solve with
+ * GNSS_CT_POS_MULTICORR on this call's records). Replaces the channel
  * loop of trackingCT_POS_updated_multicorrelator.m:41-136,170-440:
  *   - steps msIndex = 1..msPosCT/pdi (datalength = track.msPosCT, pdi = track.pdi, :46-49,
  *     :170; pdi 1 or 10), every step at that pdi, one continuous read per channel from
@@ -722,6 +723,110 @@ int gnss_vt_mc_nco_step(const gnss_signal *signal, const gnss_track *track, int3
  * (:504); everything else is gnss_vt_nav_update's. */
 int gnss_vt_mc_nav_update(gnss_vt_nav *nav, const double *codeError, const double *codeFreq,
                           const double *carrFreq, gnss_vt_navsol *sol);
+
+/* ---- trackingCT_POS_updated.m, the positioning half: navSolutionsCT ---------------------------
+ * Additive within ABI v13, like the 25-tap loop above: one status, two structs and one entry
+ * point, no existing layout or meaning changes and gnss_abi_version() stays 13; a caller detects
+ * the entry point by symbol. Line cites are of trackingCT_POS_updated.m unless marked.
+ *
+ * Positioning does not feed back into the scalar loops, so it runs as a pass over the records of
+ * gnss_tracking_ct_pos / gnss_tracking_ct_mc (:147-171, :420-565, with olspos.m, hmat.m and
+ * LS_SA_code_Vel.m; fp64 in the reference's association order, -ffp-contract=off):
+ *   - sampleStartMea = max(sampleStart) + 1 (:160), measSampleStep = fix(Fs * navSolPeriod / 1000)
+ *     * dataType (:164), currMeasSample = sampleStartMea + measSampleStep * posIndex (:423);
+ *   - at tracking step Index an epoch fires iff every channel's absoluteSample(Index) >
+ *     currMeasSample (:427-435): at most one epoch per step, so with navSolPeriod shorter than the
+ *     step the solution lags and does not catch up;
+ *   - per channel, index = (first i with absoluteSample(i) > currMeasSample) - 1 (:442-447;
+ *     index = 0 -> GNSS_EINDEX, MATLAB raises at :450) and codePhaseMeas = remChip(index) +
+ *     (codeFreq(index) / Fs) * ((currMeasSample - absoluteSample(index)) / dataType) (:450-453);
+ *   - transmitTime (:455-457), GNSS_CT_POS_UPDATED: codePhaseMeas / codelength / 1000 + ((index -
+ *     ms1 - countinx(s)) * pdi + (ms1 + countinx(s)) - (nav1 + sfb1 * 20)) / 1000 + TOW1 with pdi
+ *     the loop variable as the LAST channel's branch left it at step Index (1 if Index <= ms1 +
+ *     countinx(n), else 10; :183-184,294-295) and ms1 = msToProcessCT_1ms; GNSS_CT_POS_MULTICORR
+ *     (trackingCT_POS_updated_multicorrelator.m:481-483): codePhaseMeas / codelength / 1000 +
+ *     (index - (nav1 + sfb1 * 20)) / 1000 + TOW1 whatever pdi is;
+ *   - first fix: localTime = max(transmitTime) + 75 / 1000 (:462-465); pseudorange = (localTime -
+ *     transmitTime) * cSpeed (:466); after the fit localTime -= clkBias / cSpeed (recorded, :550-551),
+ *     then localTime += measSampleStep / Fs (:554);
+ *   - az / el / iono / tropo refresh when counter_corr reaches corrUpt (:489-502), stale values in
+ *     between: corrUpt = 10 and counters 9 at the start (:128-130); GNSS_CT_POS_UPDATED: every step
+ *     in which any channel runs the 10-ms branch sets corrUpt = 1 and the counters 0 (:301-302)
+ *     before that step's epoch, so every 10th epoch until the first channel switches, every epoch
+ *     after; GNSS_CT_POS_MULTICORR: corrUpt = 0.01 / (pdi * ms) throughout;
+ *   - olspos.m warm-started from the last estusr_wls (first [cnslxyz 0]), tol 1e-3, beta = H \ y by
+ *     Householder QR with column pivoting until norm(beta) <= tol (a NaN beta ends the loop as in
+ *     MATLAB); the reference has no iteration cap: GNSS_ENOCONV after 50. DOP from inv(H' * H);
+ *   - LS_SA_code_Vel.m with lambda = 0.190293672798365 on carrFreq - IF, carrFreq the loop's
+ *     current value, i.e. the record at row Index (not index) (:513-514);
+ *   - fewer than 4 channels: GNSS_EARG (hmat.m:10). No epoch reached: rows = 0, GNSS_OK.
+ * sampleEndMea (:161) is computed by the reference and never used. */
+#define GNSS_ENOCONV    6  /* olspos.m's iteration did not converge within 50 steps (the
+                              reference has no cap and would spin)                           */
+#define GNSS_CT_POS_UPDATED    0
+#define GNSS_CT_POS_MULTICORR  1
+
+typedef struct gnss_ct_pos_cfg {
+    int32_t n;                  /* channels: the first n of the record set, 4..GNSS_VT_MAX_CH   */
+    int32_t mode;               /* GNSS_CT_POS_UPDATED / GNSS_CT_POS_MULTICORR                   */
+    int32_t dataType;           /* file.dataType                                                 */
+    int32_t msToProcessCT_1ms;  /* track.msToProcessCT_1ms (GNSS_CT_POS_UPDATED)                 */
+    int32_t pdi;                /* track.pdi (GNSS_CT_POS_MULTICORR: corrUpt)                    */
+    int32_t reserved;
+    double  navSolPeriod;       /* solu.navSolPeriod, ms                                         */
+    double  Fs, IF, codelength, ms;   /* signal.*                                                */
+    double  cSpeed, doy;        /* cmn.cSpeed, cmn.doy                                           */
+    double  cnslxyz[3];         /* the first warm start and the ENU origin (:36, :517)           */
+    double  ALPHA[4], BETA[4];  /* broadcast iono model (initParameters.m:29-30)                 */
+    int32_t countinx[GNSS_VT_MAX_CH];     /* by channel POSITION (:29,183; quirk A.17)           */
+    int64_t nav1[GNSS_VT_MAX_CH];         /* sbf.nav1(prn)                                       */
+    int64_t sfb1[GNSS_VT_MAX_CH];         /* eph(prn).sfb(1)                                     */
+    int64_t sampleStart[GNSS_VT_MAX_CH];  /* TckResult_Eph(prn).absoluteSample(nav1 + sfb1 * 20)
+                                             (:156; the caller's mirror reads it)                */
+    double  TOW1[GNSS_VT_MAX_CH];         /* eph(prn).TOW(1)                                     */
+    gnss_eph_sv eph[GNSS_VT_MAX_CH];      /* ephemeris(prn).*(1) (eph_idx = 1, :126)             */
+} gnss_ct_pos_cfg;
+
+/* navSolutionsCT (:509-551), caller-allocated and row-major: `cap` rows per array, `rows` written
+ * back. n = gnss_ct_pos_cfg.n values per row where marked [n]. The last four arrays are not in
+ * the reference's struct and may be NULL. GNSS_EARG if more than cap epochs fire (one per
+ * tracking step at most, so cap = the records' steps always suffices). */
+typedef struct gnss_nav_sol_ct {
+    int64_t cap;
+    int64_t rows;
+    double *rawPseudorange;   /* [n] (:509)                                                     */
+    double *usrPos;           /* [3] ECEF m                                                     */
+    double *usrVel;           /* [3] m/s                                                        */
+    double *usrPosENU;        /* [3] about cnslxyz                                              */
+    double *usrPosLLH;        /* [3] degrees, degrees, m (:529-530)                             */
+    double *clkBias;          /* [1] m                                                          */
+    double *usrVelENU;        /* [3]                                                            */
+    double *clkDrift;         /* [1] m/s                                                        */
+    double *DOP;              /* [4] GDOP PDOP HDOP VDOP (olspos.m:56-61)                       */
+    double *satEA;            /* [n] degrees                                                    */
+    double *satAZ;            /* [n] degrees                                                    */
+    double *timeTransmit;     /* [n] s                                                          */
+    double *codePhaseMeas;    /* [n] chips                                                      */
+    double *localTime;        /* [1] s, after the clock correction (:550-551)                   */
+    int64_t *Index;           /* [1] the tracking step at which the epoch fired (1-based)       */
+    int64_t *index;           /* [n] each channel's `index` (:447, 1-based)                     */
+    double  *carrFreqMeas;    /* [n] carrFreq(Index), the velocity fit's measurement            */
+    int32_t *iters;           /* [1] olspos iterations                                          */
+} gnss_nav_sol_ct;
+
+/* The pass. records: the output of gnss_tracking_ct_pos (GNSS_CT_POS_UPDATED) or
+ * gnss_tracking_ct_mc (GNSS_CT_POS_MULTICORR), or any array of that layout; read are rec (the
+ * absoluteSample, remChip, codeFreq and carrFreq series of channels 0..n-1), max_len, len (the
+ * pass runs over min(len) steps) and flags. With GNSS_OUT_DEVICE in records->flags rec is a device
+ * pointer of the context's device and the measurement table (Index, index, codePhaseMeas,
+ * carrFreq(Index): 4 values per channel and epoch) is extracted on the GPU (csrc/ctpos.hip), so
+ * the records never cross PCIe; otherwise on the host. The two tables are equal bit for bit. A
+ * record index outside the series, caught by the kernels' bound check, returns GNSS_EDEVICE with
+ * the context usable. Host records need no GPU and ctx may be NULL; device records on a context
+ * of gnss_ctx_create_multi return GNSS_EARG (no gathering across members). On an error out->rows
+ * is 0. */
+int gnss_ct_pos_solve(gnss_ctx *ctx, const gnss_ct_pos_cfg *cfg, const gnss_track_out *records,
+                      gnss_nav_sol_ct *out);
 
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
