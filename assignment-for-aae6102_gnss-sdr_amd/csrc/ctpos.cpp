@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "ctpos.h"
+#include "host.h"
 
 namespace {
 
@@ -387,3 +388,56 @@ int gnss::ct_solve_table(const gnss_ct_pos_cfg& c, const CtTable& t, gnss_nav_so
     out->rows = t.rows;
     return GNSS_OK;
 }
+
+using namespace gnss;
+using namespace gnss::host;
+
+extern "C" {
+
+// trackingCT_POS_updated.m:147-171,420-565 as a pass over the tracking records (ctpos.h): the
+// measurement table on the host or, for GNSS_OUT_DEVICE records, on the GPU, then the solver
+int gnss_ct_pos_solve(gnss_ctx* ctx, const gnss_ct_pos_cfg* cfg, const gnss_track_out* rec, gnss_nav_sol_ct* out)
+{
+    if (out) out->rows = 0;
+    if (!cfg || !rec || !out) return fail(ctx, GNSS_EARG, "gnss_ct_pos_solve: a null argument");
+    const bool on_device = (rec->flags & GNSS_OUT_DEVICE) != 0;
+    const int n = cfg->n;
+    if (n >= 1 && n < 4) return fail(ctx, GNSS_EARG, "insufficient number of satellites (hmat.m:10): %d", n);
+    if (n < 1 || n > GNSS_VT_MAX_CH) return fail(ctx, GNSS_EARG, "gnss_ct_pos_cfg.n outside 4..%d", GNSS_VT_MAX_CH);
+    if ((cfg->mode != GNSS_CT_POS_UPDATED && cfg->mode != GNSS_CT_POS_MULTICORR) ||
+        (cfg->dataType != 1 && cfg->dataType != 2) || !(cfg->Fs > 0) || !(cfg->codelength > 0) || !(cfg->ms > 0) ||
+        !(cfg->cSpeed > 0) || !(cfg->navSolPeriod > 0) || !(ct_meas_step(*cfg) >= 1) ||
+        (cfg->mode == GNSS_CT_POS_MULTICORR && cfg->pdi < 1))
+        return fail(ctx, GNSS_EARG, "gnss_ct_pos_cfg: mode, dataType, Fs, codelength, ms, cSpeed, navSolPeriod or pdi");
+    if (!rec->rec || !rec->len || rec->max_len < 1) return fail(ctx, GNSS_EARG, "gnss_ct_pos_solve: records");
+    if (out->cap < 0 || !out->rawPseudorange || !out->usrPos || !out->usrVel || !out->usrPosENU || !out->usrPosLLH ||
+        !out->clkBias || !out->usrVelENU || !out->clkDrift || !out->DOP || !out->satEA || !out->satAZ ||
+        !out->timeTransmit || !out->codePhaseMeas || !out->localTime || !out->Index)
+        return fail(ctx, GNSS_EARG, "gnss_nav_sol_ct: a null array");
+    CtRecords r{rec->rec, rec->max_len, rec->len[0], n};
+    for (int s = 0; s < n; s++) {
+        if (rec->len[s] < 0 || rec->len[s] > rec->max_len)
+            return fail(ctx, GNSS_EARG, "gnss_ct_pos_solve: len[%d] outside 0..max_len", s);
+        r.L = std::min(r.L, rec->len[s]);
+    }
+    CtTable table;
+    std::string err;
+    int st;
+    if (on_device) {
+        if (!ctx) return GNSS_EARG;
+        if (!ctx->members.empty())
+            return fail(ctx, GNSS_EARG, "gnss_ct_pos_solve: device records on a multi-device context");
+        HIP_TRY(hipSetDevice(ctx->device));
+        st = ct_extract_device(*cfg, r, out->cap, ctx->stream, &table, &err);
+    } else {
+        st = ct_extract_host(*cfg, r, out->cap, &table, &err);
+    }
+    if (st == GNSS_OK) st = ct_solve_table(*cfg, table, out, &err);
+    if (st != GNSS_OK) {
+        out->rows = 0;
+        return fail(ctx, st, "%s", err.c_str());
+    }
+    return GNSS_OK;
+}
+
+}  // extern "C"

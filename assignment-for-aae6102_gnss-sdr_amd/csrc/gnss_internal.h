@@ -1,5 +1,5 @@
 // gnss_internal.h — internal declarations shared by the C-ABI host code
-// (gnss_api.cpp) and the gfx950 kernels (track.hip, acq.hip, synth.hip).
+// (host.h and its .cpp files) and the gfx950 kernels (track.hip, acq.hip, synth.hip).
 // Not part of the public boundary (that is include/gnss_mi355x.h).
 #pragma once
 

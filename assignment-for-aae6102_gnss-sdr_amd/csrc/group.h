@@ -86,7 +86,7 @@ inline int acquisition_status(const std::vector<int>& st, int merged_n)
 }
 
 // The status of a sharded tracking call. One context decides it over its channels in
-// order (gnss_api.cpp, tracking_impl): GNSS_ENODATA ("Not enough raw data") if any channel
+// order (api_track.cpp, tracking_impl): GNSS_ENODATA ("Not enough raw data") if any channel
 // ran short, else the status of the first failing channel. Member k reports its status and
 // the position, in the call's channel list, of the channel that set it (-1: failed before any
 // channel ran, i.e. an argument error that every member shares). The same rule over the members' reports gives
@@ -121,7 +121,7 @@ inline int tracking_status(const std::vector<TrackStatus>& st)
 }
 
 // CarrTime = k/Fs as the tracking kernels form it (k * RN(1/Fs) plus one FMA correction)
-// equals the IEEE quotient for every k in [0, kmax] (exhaustive; gnss_api.cpp caches it per
+// equals the IEEE quotient for every k in [0, kmax] (exhaustive; host.h caches it per
 // (Fs, kmax) behind a mutex, since a group's member threads reach it concurrently).
 inline int reciprocal_exact(double Fs, int64_t kmax)
 {
@@ -136,7 +136,7 @@ inline int reciprocal_exact(double Fs, int64_t kmax)
 }
 
 // reciprocal_exact, cached per (Fs, kmax). A multi-device context reaches it from one host
-// thread per device (gnss_api.cpp, for_members), so the cache is guarded: the check
+// thread per device (host.h, for_members), so the cache is guarded: the check
 // runs outside the lock (a pure function of the key: two threads that miss together compute
 // the same answer), the lookup and the insert under it.
 inline int reciprocal_exact_cached(double Fs, int64_t kmax)

@@ -1,7 +1,7 @@
 // vt_mc.cpp — the host half of a 25-tap vector-tracking step
 // (trackingVT_POS_updated_multicorrelator.m:151-470): read sizing, the 25 replica colons and
 // their table-index range, and the scalar end from the 50 sums (vt_mc_prepare / vt_mc_finish in
-// vt_mc.h: the source the loop in gnss_api.cpp runs). Compiled with -ffp-contract=off like the
+// vt_mc.h: the source the loop in api_vt.cpp runs). Compiled with -ffp-contract=off like the
 // rest of the library, so every operation rounds as MATLAB's does.
 // Reference: SDR_MATLAB-main/acqtckpos/trackingVT_POS_updated_multicorrelator.m.
 #include <cmath>

@@ -1,5 +1,5 @@
 // vt_mc.h — the 25-tap vector-tracking step (trackingVT_POS_updated_multicorrelator.m:151-470):
-// the scalar arithmetic shared by the host half (vt_mc.cpp), the loop (gnss_api.cpp) and the
+// the scalar arithmetic shared by the host half (vt_mc.cpp), the loop (api_vt.cpp) and the
 // correlator kernel (vt_mc.hip), compiled with -ffp-contract=off on every side so each
 // operation rounds as MATLAB's does. Line cites are of that file unless they name another.
 // What differs from the plain loop (vt_prepare / vt_finish in gnss_internal.h): 25 real

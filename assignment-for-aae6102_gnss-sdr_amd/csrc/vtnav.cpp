@@ -5,7 +5,7 @@
 // with Get_UNB3_Model.m / Trop_Saastamoinen_UNB3_Components.m / Trop_Black_Eisner_Map.m,
 // erotcorr.m). Host code: a step's navigation work is a few hundred scalar fp64 operations
 // and one 2n x 2n inverse, latency-bound and serial across steps, so it stays on the CPU
-// beside the VT correlator kernel (vt.hip); gnss_tracking_vt (gnss_api.cpp) alternates the
+// beside the VT correlator kernel (vt.hip); gnss_tracking_vt (api_vt.cpp) alternates the
 // two. Built with -ffp-contract=off: every operation rounds separately, in the reference's
 // association order (line cites inline).
 #include <algorithm>

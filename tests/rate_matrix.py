@@ -4,7 +4,7 @@ other tracking test runs on, the oracle's results on it (cached per rate, tap co
 format: they do not depend on the lane span or on the persistent / per-step choice), and the
 single-step case list. A plain helper module, no fixtures.
 
-What each rate brings (gnss_api.cpp's lane geometry, track.hip's carrier table and step sizing):
+What each rate brings (track_geom.h's lane geometry, track.hip's carrier table and step sizing):
   urban26    BASELINE config 4's signal: IF = 0, so the carrier is the Doppler alone (negative
              for PRNs 5 and 20); 32-sample lanes refused, 16-sample lanes in the 10-ms phase
   l1_16m     Fs*ms = 16367.6 is no integer (Sample = ceil = 16368), f/Fs = 0.25, and the
@@ -173,7 +173,7 @@ def oracle_steps(rate):
     return tuple(oracle_step(rate, c) for c in step_cases(rate))
 
 
-# ---- the engine's lane geometry (gnss_api.cpp: sub_ok / sub_for / bpc_for), restated ----------
+# ---- the engine's lane geometry (csrc/track_geom.h: sub_ok / sub_for / bpc_for), restated ------
 def sub_ok(Fs, sub):
     """A lane of 8*sub samples holds at most one chip boundary per tap, with the 1.1 margin."""
     return 8.0 * sub * 1.1 * FC / Fs < 1.0

@@ -41,7 +41,7 @@ def rate_report():
         f.write("Rate-matrix parity, GPU vs CPU oracle (tests/test_gpu_rates.py): measured values, not thresholds.\n"
                 "Bounds asserted: step sums 1e-12 of the RMS; P/E/L 1e-8 of the series RMS; 11-tap array 1e-10;\n"
                 "SNR 1e-6 dB (fp64) / 1e-3 dB (fp32); VT sums 1e-9 of |P|.\n"
-                "Lane geometry = the engine's rule (gnss_api.cpp sub_ok / sub_for / bpc_for) as restated in\n"
+                "Lane geometry = the engine's rule (track_geom.h sub_ok / sub_for / bpc_for) as restated in\n"
                 "tests/rate_matrix.py: lane span in samples / blocks per channel, 1-ms and 10-ms steps.\n\n")
         for rate, (Fs, IF) in rm.RATES.items():
             g1, g10 = rm.lane_geometry(Fs, 1), rm.lane_geometry(Fs, 10)

@@ -50,7 +50,7 @@ def test_multi_device_bookkeeping(tmp_path):
     """gnss_ctx_create_multi's dealing and merging (csrc/group.h): the PRN / channel deal, the
     Acquired / diag rows merged back into PRN-list order, and a sharded call's status equal the
     one-context results (acquisition.m:47-80,84-85; trackingCT.m:22-528 and the channel loop's
-    status rule in gnss_api.cpp). Host C++ only."""
+    status rule in api_track.cpp). Host C++ only."""
     cxx = shutil.which("g++") or HIPCC
     src = os.path.join(ROOT, "tests", "native", "group_test.cpp")
     exe = tmp_path / "group_test"
@@ -67,6 +67,33 @@ def test_multi_device_bookkeeping(tmp_path):
         r = subprocess.run([str(tsan)], capture_output=True, text=True)
         if "FATAL: ThreadSanitizer: unexpected memory mapping" not in r.stderr:  # (TSan vs this kernel's ASLR)
             assert r.returncode == 0 and "WARNING: ThreadSanitizer" not in r.stderr, r.stdout + r.stderr[-3000:]
+
+
+def test_track_geometry_equals_restatement(tmp_path):
+    """The engine's own lane-span and grid rule (csrc/track_geom.h, called by api_track.cpp's
+    tracking_impl and gnss_correlate_step) gives the (sub, blocks per channel) of
+    rate_matrix.lane_geometry, the independent restatement the GPU rate tests use, at every rate
+    of the matrix and at 58 MHz, for 1-ms and 10-ms steps and every GNSS_OPT_FORCE_SUB value; the
+    program itself checks the int16 / 25-tap spans, rejected overrides and the virtual-block
+    search. Host C++ only, once more under AddressSanitizer and UBSan."""
+    import rate_matrix as rm
+    table = tmp_path / "geometry.txt"
+    with open(table, "w") as f:
+        for Fs in [fs for fs, _ in rm.RATES.values()] + [58e6]:
+            for pdi in (1, 10):
+                for forced in (0, 1, 2, 3, 4):
+                    sub, bpc = rm.lane_geometry(Fs, pdi, forced)
+                    f.write(f"{Fs!r} {rm.sample_of(Fs)} {pdi} {forced} {sub} {bpc}\n")
+    cxx = shutil.which("g++") or HIPCC
+    src = os.path.join(ROOT, "tests", "native", "track_geom.cpp")
+    for name, flags in (("track_geom", ["-O2"]),
+                        ("track_geom_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = tmp_path / name
+        subprocess.run([cxx, *flags, "-std=c++17", "-ffp-contract=off", "-o", str(exe), src], check=True,
+                       capture_output=True)
+        r = subprocess.run([str(exe), str(table)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert "cases 60, mismatches 0" in r.stdout
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
