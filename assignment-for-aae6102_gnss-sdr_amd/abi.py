@@ -199,6 +199,27 @@ class GnssNavSolCt(C.Structure):
 
 ADDED_STRUCTS.update({"gnss_ct_pos_cfg": "GnssCtPosCfg", "gnss_nav_sol_ct": "GnssNavSolCt"})
 
+# ACF/CalculateFeatures.m (gnss_acf_features; additive within ABI v13): the script's parameters
+# (:172-179, :186) and the per-window outputs in data_labeled's column order (:277-282)
+ACF_DEFAULTS = dict(ind_start=1, numOverLap=100, corrSpacing=0.05, maxDelay=0.6,
+                    a=(4092.9779845217, 340.423503277404, -2.99026922880033, 0.0251763660254827))
+ACF_FIELDS = ["meanMax", "F1", "F2", "varDelay", "meanCodeDisc", "varCodeDisc"]
+
+
+class GnssAcfCfg(C.Structure):
+    _fields_ = [("n", C.c_int32), ("ind_start", C.c_int32), ("numOverLap", C.c_int32), ("reserved", C.c_int32),
+                ("corrSpacing", C.c_double), ("maxDelay", C.c_double), ("a", C.c_double * 4),
+                ("prn", C.c_int32 * VT_MAX_CH), ("ele", C.c_double * VT_MAX_CH)]
+
+
+class GnssAcfOut(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("windows", C.POINTER(C.c_int64))] + \
+               [(f, C.POINTER(C.c_double)) for f in ACF_FIELDS] + \
+               [("maxCorrInd", C.c_void_p), ("corr", C.c_void_p)]
+
+
+ADDED_STRUCTS.update({"gnss_acf_cfg": "GnssAcfCfg", "gnss_acf_out": "GnssAcfOut"})
+
 
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
@@ -300,6 +321,9 @@ PROTOTYPES = {
     # trackingCT_POS_updated.m's positioning half (additive within ABI v13: detected by symbol)
     "gnss_ct_pos_solve": (C.c_int, [C.c_void_p, C.POINTER(GnssCtPosCfg), C.POINTER(GnssTrackOut),
                                     C.POINTER(GnssNavSolCt)]),
+    # ACF/CalculateFeatures.m over the 25-tap records (additive within ABI v13: detected by symbol)
+    "gnss_acf_features": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfCfg), C.POINTER(GnssTrackOut), C.c_int32,
+                                    C.POINTER(GnssAcfOut)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

@@ -510,7 +510,7 @@ def mc_result(Acquired, buf: TrackOutBuffers, channels=None, fields=None) -> Str
 
 def trackingCT_POS_updated_multicorrelator(file, signal, track, Acquired, *,
                                            ctx: Context | None = None, channels=None,
-                                           raw: bool = False):
+                                           raw: bool = False, device_records: bool = False):
     """The tracking loop of trackingCT_POS_updated_multicorrelator.m (:41-136, :170-440) on
     the GPU -> (TckResultCT_mltCorr, CN0_CT).
 
@@ -518,7 +518,9 @@ def trackingCT_POS_updated_multicorrelator(file, signal, track, Acquired, *,
     it) and track.pdi (:46, 1 or 10) give msPosCT/pdi steps, every one at that pdi. The 25
     taps at Spacing = 0.6:-0.05:-0.6 are all recorded; E/P/L = Spacing(3)/(13)/(23) drive
     the loops. The positioning half (:446-590) is ct_positioning(..., mode="multicorr") on
-    the returned records.
+    the returned records. With device_records the records and taps stay in HBM
+    (DeviceTrackOutBuffers, GNSS_OUT_DEVICE): with raw they are returned as they lie, for
+    acf_features / ct_positioning to read there.
     """
     ctx = ctx or default_context()
     nsv = len(Acquired.sv)
@@ -528,12 +530,18 @@ def trackingCT_POS_updated_multicorrelator(file, signal, track, Acquired, *,
     a = to_c_acquired(Acquired)
     msPosCT, pdi = int(track.msPosCT), int(track.pdi)
     nsteps = msPosCT // pdi if pdi > 0 else 0
-    buf = TrackOutBuffers(nsv, track, abi.MC_TAPS, ctPOS=max(nsteps, 1))
+    if device_records:
+        buf = DeviceTrackOutBuffers(nsv, track, abi.MC_TAPS, device=f"cuda:{ctx.device}", ctPOS=max(nsteps, 1))
+        buf.sync_producer()
+    else:
+        buf = TrackOutBuffers(nsv, track, abi.MC_TAPS, ctPOS=max(nsteps, 1))
     st = ctx.lib.gnss_tracking_ct_mc(ctx.h, C.byref(f), C.byref(s), C.byref(t), C.byref(a),
                                      msPosCT, pdi, C.byref(buf.c))
     ctx.check(st)
     if raw:
         return buf
+    if device_records:
+        buf = buf.host()
     cn0 = buf.CN0[: buf.c.cn0_rows].copy()
     return mc_result(Acquired, buf, channels), cn0
 
@@ -1168,3 +1176,146 @@ def trackingCT_POS_updated(file, signal, track, cmn, Acquired, TckResult_Eph, cn
                          TckResult_Eph=TckResult_Eph, ctx=ctx, ALPHA_=ALPHA_, BETA_=BETA_)
     hb = buf.host() if device_records else buf
     return build_tck_result(Acquired, hb, None, abi.FIELDS_POS), nav
+
+
+# ---------------------------------------------------------------------------
+# ACF/CalculateFeatures.m: the multipath / NLOS features of the 25-tap records
+# ---------------------------------------------------------------------------
+def _acf_pack(TckResults_multiCorr, prnList):
+    """The per-PRN structs of a 25-tap loop packed into the gnss_track_out layout: taps
+    [n][2][25][max_len] and the code discriminator in the DLLdiscri slot. The scalar loops'
+    structs carry taps_i / taps_q (25 x steps) and DLLdiscri or codeError, the vector loop's
+    (TckResultVT_mltCorr) tap_i / tap_q (steps x 25) and codeError."""
+    chans = []
+    for p in prnList:
+        e = _struct_of(TckResults_multiCorr, p)
+        if hasattr(e, "taps_i"):
+            ti, tq = np.asarray(e.taps_i, dtype=np.float64), np.asarray(e.taps_q, dtype=np.float64)
+        else:
+            ti, tq = np.asarray(e.tap_i, dtype=np.float64).T, np.asarray(e.tap_q, dtype=np.float64).T
+        d = np.asarray(e.DLLdiscri if hasattr(e, "DLLdiscri") else e.codeError, dtype=np.float64).ravel()
+        if ti.shape[0] != abi.MC_TAPS or tq.shape != ti.shape or len(d) < ti.shape[1]:
+            raise ValueError(f"PRN {p}: 25 taps of I and Q and a code discriminator per step")
+        chans.append((ti, tq, d))
+    n = len(chans)
+    lens = np.array([c[0].shape[1] for c in chans], dtype=np.int64)
+    max_len = max(int(lens.max()) if n else 1, 1)
+    rec = np.zeros((n, abi.NFIELDS, max_len))
+    taps = np.zeros((n, 2, abi.MC_TAPS, max_len))
+    for i, (ti, tq, d) in enumerate(chans):
+        taps[i, 0, :, : lens[i]], taps[i, 1, :, : lens[i]] = ti, tq
+        rec[i, abi.FIELDS.index("DLLdiscri"), : lens[i]] = d[: lens[i]]
+    o = abi.GnssTrackOut()
+    o.max_len = max_len
+    o.rec = rec.ctypes.data_as(C.POINTER(C.c_double))
+    o.taps = taps.ctypes.data_as(C.POINTER(C.c_double))
+    o.len = lens.ctypes.data_as(C.POINTER(C.c_int64))
+    return o, (rec, taps, lens)
+
+
+def acf_features(records, prnList, eleList, *, ctx: Context | None = None, want_index: bool = False,
+                 want_corr: bool = False, **params):
+    """The features of ACF/CalculateFeatures.m per channel (gnss_acf_features): a namespace of
+    prn, ele, windows [n] and, per name of abi.ACF_FIELDS, a list of n arrays (one value per
+    100-ms window): meanMax, F1 = meanMax / expectedCorr(ele), F2 = -meanDelay, varDelay,
+    meanCodeDisc, varCodeDisc.
+
+    `records`: the raw TrackOutBuffers of a 25-tap loop (channel c is prnList[c]), or the per-PRN
+    structs the loops return (looked up by PRN, packed on the host). DeviceTrackOutBuffers stay in
+    HBM: the kernels read them where they lie and only the features come back. params: ind_start,
+    numOverLap, corrSpacing, maxDelay, a (abi.ACF_DEFAULTS). want_index / want_corr add
+    maxCorrInd [n][max_len] (1-based arg-max per row) and corr [n][25][max_len], numpy arrays for
+    host records and torch tensors on the device for device records. Host records need no GPU.
+    """
+    unknown = set(params) - set(abi.ACF_DEFAULTS)
+    if unknown:
+        raise TypeError(f"acf_features: unknown parameter(s) {sorted(unknown)}")
+    par = dict(abi.ACF_DEFAULTS, **params)
+    prn = [int(p) for p in np.atleast_1d(prnList)]
+    ele = [float(e) for e in np.atleast_1d(eleList)]
+    n = len(prn)
+    if len(ele) != n:
+        raise ValueError("prnList and eleList differ in length")
+    if n > abi.VT_MAX_CH:
+        raise ValueError(f"acf_features takes at most {abi.VT_MAX_CH} channels")
+    on_device = isinstance(records, DeviceTrackOutBuffers)
+    if isinstance(records, TrackOutBuffers):
+        if records.taps is None or records.taps.shape[2] != abi.MC_TAPS or records.taps.shape[0] < n:
+            raise ValueError("acf_features: the records of a 25-tap loop, one channel per PRN")
+        lens, max_len = records.len, records.max_len
+        if on_device:
+            rec, keep = records.c, records
+            ctx = ctx or default_context()
+            records.sync_producer()
+        else:  # (a host copy of device buffers still carries their gnss_track_out: build it anew)
+            keep = (np.ascontiguousarray(records.rec, dtype=np.float64),
+                    np.ascontiguousarray(records.taps, dtype=np.float64),
+                    np.ascontiguousarray(records.len, dtype=np.int64))
+            rec = abi.GnssTrackOut()
+            rec.max_len = max_len
+            rec.rec = keep[0].ctypes.data_as(C.POINTER(C.c_double))
+            rec.taps = keep[1].ctypes.data_as(C.POINTER(C.c_double))
+            rec.len = keep[2].ctypes.data_as(C.POINTER(C.c_int64))
+    else:
+        rec, keep = _acf_pack(records, prn)
+        lens, max_len = keep[2], rec.max_len
+    cfg = abi.GnssAcfCfg()
+    cfg.n, cfg.ind_start, cfg.numOverLap = n, int(par["ind_start"]), int(par["numOverLap"])
+    cfg.corrSpacing, cfg.maxDelay = float(par["corrSpacing"]), float(par["maxDelay"])
+    cfg.a[:] = [float(x) for x in par["a"]]
+    cfg.prn[:n], cfg.ele[:n] = prn, ele
+    nov = max(cfg.numOverLap, 1)
+    cap = max([max(int(l) - cfg.ind_start, 0) // nov for l in lens[:n]] + [1])
+    out = abi.GnssAcfOut()
+    out.cap = cap
+    windows = np.zeros(max(n, 1), dtype=np.int64)
+    out.windows = windows.ctypes.data_as(C.POINTER(C.c_int64))
+    arr = {f: np.zeros((max(n, 1), cap)) for f in abi.ACF_FIELDS}
+    for f in abi.ACF_FIELDS:
+        setattr(out, f, arr[f].ctypes.data_as(C.POINTER(C.c_double)))
+    ind = corr = None
+    if on_device and (want_index or want_corr):
+        import torch
+        if want_index:
+            ind = torch.zeros((n, max_len), dtype=torch.uint8, device=records.device)
+            out.maxCorrInd = ind.data_ptr()
+        if want_corr:
+            corr = torch.zeros((n, abi.MC_TAPS, max_len), dtype=torch.float64, device=records.device)
+            out.corr = corr.data_ptr()
+        torch.cuda.current_stream(records.device).synchronize()
+    elif want_index or want_corr:
+        if want_index:
+            ind = np.zeros((n, max_len), dtype=np.uint8)
+            out.maxCorrInd = ind.ctypes.data
+        if want_corr:
+            corr = np.zeros((n, abi.MC_TAPS, max_len))
+            out.corr = corr.ctypes.data
+    lib = abi.load()
+    h = ctx.h if ctx is not None else None
+    st = lib.gnss_acf_features(h, C.byref(cfg), C.byref(rec), abi.MC_TAPS, C.byref(out))
+    if st != abi.OK:
+        msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
+        raise abi.GnssError(st, msg)
+    res = SimpleNamespace(prn=prn, ele=ele, windows=windows[:n].copy(), maxCorrInd=ind, corr=corr)
+    for f in abi.ACF_FIELDS:
+        setattr(res, f, [arr[f][c, : windows[c]].copy() for c in range(n)])
+    return res
+
+
+def CalculateFeatures(TckResults_multiCorr, prnList, eleList, *, ctx: Context | None = None, **params):
+    """ACF/CalculateFeatures.m:165-296 -> data_labeled, (1 + sum of the channels' windows) x 8:
+    the script's all-zero first row (:165), then per PRN of prnList and per 100-ms window
+    [prn, ele, meanMax, F1, F2, F3 = varDelay, F4 = meanCodeDisc, F5 = varCodeDisc] (:276-288).
+
+    TckResults_multiCorr is what any of the three 25-tap loops returns (trackingCT_multiCorr,
+    trackingCT_POS_updated_multicorrelator, trackingVT_POS_updated_multicorrelator) or their raw
+    buffers, as for acf_features; prnList / eleList replace the script's hard-coded lists
+    (:167-168) and params its hard-coded parameters (:172-179, :186). The plots of :298-323 are
+    not drawn."""
+    f = acf_features(TckResults_multiCorr, prnList, eleList, ctx=ctx, **params)
+    rows = [np.zeros((1, 8))]
+    for c, (p, e) in enumerate(zip(f.prn, f.ele)):
+        w = int(f.windows[c])
+        rows.append(np.column_stack([np.full(w, float(p)), np.full(w, e)] +
+                                    [getattr(f, k)[c] for k in abi.ACF_FIELDS]).reshape(w, 8))
+    return np.vstack(rows)

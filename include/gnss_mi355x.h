@@ -828,6 +828,77 @@ typedef struct gnss_nav_sol_ct {
 int gnss_ct_pos_solve(gnss_ctx *ctx, const gnss_ct_pos_cfg *cfg, const gnss_track_out *records,
                       gnss_nav_sol_ct *out);
 
+/* ---- ACF/CalculateFeatures.m (additive within ABI v13; detected by symbol) ----------------
+ * The multipath / NLOS features of the 25-tap records, as a pass over the records of
+ * gnss_tracking_ct_mc, gnss_tracking_ct_multicorr or a packed trackingVT_..._multicorrelator
+ * run. All arithmetic fp64, every operation rounded on its own, every sum left to right. Per
+ * channel with L = len rows (line cites of CalculateFeatures.m):
+ *   - corr(i, j) = sqrt(I*I + Q*Q) of tap j-1 in storage order, j = 1..25 (:197-225; the order
+ *     of :198-224 is the storage order E_060 ... E_005, P, L005 ... L060);
+ *   - cenDelay = maxDelay / corrSpacing + 1 in fp64 (:176; 12.999999999999998 for the defaults,
+ *     so a prompt peak contributes 8.88e-17 chip, not 0);
+ *   - windows m = 1 .. floor((L - ind_start) / numOverLap) (:234; a record whose length is a
+ *     multiple of numOverLap loses its last window), sample n of window m is row
+ *     r = ind_start - 1 + n + (m - 1) * numOverLap;
+ *   - maxCorrInd(m, n) = the first index of the largest corr(r, :) (:236; a NaN counts as
+ *     missing, an all-NaN row gives 1); maxCorr(n) = corr(r, 13), the prompt magnitude, which
+ *     overwrites the maximum (:237);
+ *   - tmpDelay(n) = (maxCorrInd(m, n) - mean(maxCorrInd(m, :))) * corrSpacing with the mean over
+ *     the row as it stands at that moment (:238): S_n / n in a channel's first window (the row
+ *     grows; maxCorrInd is cleared per PRN, :294), S_n / numOverLap in every later one (the row
+ *     is already numOverLap wide and zero filled), S_n the exact sum of the first n indices;
+ *   - meanMax = sum(maxCorr) / numOverLap (:260), meanDelay = sum((maxCorrInd(m, :) - cenDelay) *
+ *     corrSpacing) / numOverLap (:270), varDelay = sum(tmpDelay.^2) / numOverLap (:271),
+ *     meanCodeDisc = mean(d), varCodeDisc = var(d) (:273-274; two passes, n - 1 below) with d the
+ *     GNSS_F_DLLdiscri (= codeError) series of the window's rows;
+ *   - F1 = meanMax / expectedCorr, expectedCorr = a[0] + a[1]*ele + a[2]*ele^2 + a[3]*ele^3 left
+ *     to right with pow (:186-188); F2 = -(meanDelay + 0.00) * 1 (:279).
+ * The plotting tail (:298-323) is not part of it. The reference ships no output of this script:
+ * the definition is this restatement. */
+typedef struct gnss_acf_cfg {
+    int32_t n;                  /* channels: the first n of the record set, 1..GNSS_VT_MAX_CH */
+    int32_t ind_start;          /* :178, 1-based; default 1                                   */
+    int32_t numOverLap;         /* :179, rows per window, 2..4096; default 100                */
+    int32_t reserved;
+    double  corrSpacing;        /* :173, default 0.05                                         */
+    double  maxDelay;           /* :174, default 0.6                                          */
+    double  a[4];               /* :186, default 4092.9779845217 340.423503277404
+                                   -2.99026922880033 0.0251763660254827                       */
+    int32_t prn[GNSS_VT_MAX_CH];/* prnList, echoed by the caller's data_labeled               */
+    double  ele[GNSS_VT_MAX_CH];/* eleList, degrees                                           */
+} gnss_acf_cfg;
+
+/* Caller-allocated. The six feature arrays are row-major [n][cap] host arrays; channel c's
+ * window m (0-based) is at [c * cap + m], windows[c] of them written. maxCorrInd and corr are
+ * optional (NULL: not wanted) and cover every row i < len[c] of a channel, in a window or not:
+ * maxCorrInd[c * max_len + i] is the 1-based arg-max of row i, corr[(c * 25 + j) * max_len + i]
+ * the magnitude of tap j. With GNSS_OUT_DEVICE in records->flags these two are DEVICE pointers
+ * (they are as large as the records), otherwise host pointers. */
+typedef struct gnss_acf_out {
+    int64_t  cap;             /* windows per channel the arrays hold                          */
+    int64_t *windows;         /* [n]                                                          */
+    double  *meanMax;         /* mean prompt magnitude (:260)                                 */
+    double  *F1;              /* meanMax / expectedCorr (:278)                                */
+    double  *F2;              /* -(meanDelay + 0.00) * 1, chips (:279)                        */
+    double  *varDelay;        /* F3 (:271)                                                    */
+    double  *meanCodeDisc;    /* F4 (:273)                                                    */
+    double  *varCodeDisc;     /* F5 (:274)                                                    */
+    uint8_t *maxCorrInd;      /* [n][max_len], 1..25; may be NULL                             */
+    double  *corr;            /* [n][25][max_len]; may be NULL                                */
+} gnss_acf_out;
+
+/* The pass. records: rec (the GNSS_F_DLLdiscri series), taps [nsv][2][25][max_len], len,
+ * max_len and flags are read; n_taps is the records' tap count and must be GNSS_MC_TAPS. Host
+ * records need no GPU and ctx may be NULL; with GNSS_OUT_DEVICE rec and taps are device pointers
+ * of the context's device and the pass runs on the GPU (csrc/acf.hip): one streaming pass over
+ * the taps, only the features cross PCIe. Both paths give the same bits in every output. Device
+ * records on a context of gnss_ctx_create_multi return GNSS_EARG. GNSS_EARG also for n_taps !=
+ * 25, n outside 1..GNSS_VT_MAX_CH, numOverLap outside 2..4096, ind_start < 1, corrSpacing <= 0,
+ * len[c] outside 0..max_len and more windows than cap: all checked on the host before any
+ * launch, so no kernel indexes past len[c] rows of a max_len series. */
+int gnss_acf_features(gnss_ctx *ctx, const gnss_acf_cfg *cfg, const gnss_track_out *records,
+                      int32_t n_taps, gnss_acf_out *out);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
