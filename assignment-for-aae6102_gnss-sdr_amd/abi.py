@@ -232,6 +232,26 @@ class GnssSynth(C.Structure):
                 ("seed", C.c_uint64), ("n_sv", C.c_int32), ("sv", GnssSynthSv * MAX_SV)]
 
 
+# Multipath / NLOS scenes (gnss_synth_scene_device / _host; additive within ABI v13): gnss_synth's
+# fields, a gain per SV on its direct signal and the reflected rays
+MAX_RAYS = 128
+
+
+class GnssSynthRay(C.Structure):
+    _fields_ = [("sv", C.c_int32), ("reserved", C.c_int32), ("delay_chips", C.c_double), ("gain", C.c_double),
+                ("phase0_cycles", C.c_double), ("fade_hz", C.c_double), ("t_on", C.c_uint64),
+                ("t_off", C.c_uint64)]
+
+
+class GnssSynthScene(C.Structure):
+    _fields_ = [("Fs", C.c_double), ("IF", C.c_double), ("noise_sigma", C.c_double),
+                ("seed", C.c_uint64), ("n_sv", C.c_int32), ("sv", GnssSynthSv * MAX_SV),
+                ("los_gain", C.c_double * MAX_SV), ("n_ray", C.c_int32), ("ray", GnssSynthRay * MAX_RAYS)]
+
+
+ADDED_STRUCTS.update({"gnss_synth_ray": "GnssSynthRay", "gnss_synth_scene": "GnssSynthScene"})
+
+
 # exported symbols and their prototypes (checked by tests against the header)
 PROTOTYPES = {
     "gnss_abi_version": (C.c_int, []),
@@ -278,6 +298,9 @@ PROTOTYPES = {
                                       C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "gnss_synth_if_device": (C.c_int, [C.c_void_p, C.POINTER(GnssSynth), C.c_uint64, C.c_uint64,
                                        C.c_void_p]),
+    "gnss_synth_scene_device": (C.c_int, [C.c_void_p, C.POINTER(GnssSynthScene), C.c_uint64, C.c_uint64,
+                                          C.c_void_p]),
+    "gnss_synth_scene_host": (C.c_int, [C.POINTER(GnssSynthScene), C.c_uint64, C.c_uint64, C.c_void_p, C.c_int]),
     "gnss_tracking_vt_run": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal),
                                        C.POINTER(GnssTrack), C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(GnssVtChan), C.POINTER(C.c_double), C.POINTER(GnssVtOut)]),

@@ -26,7 +26,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import abi
+from . import abi, synth
 
 
 # ---------------------------------------------------------------------------
@@ -1319,3 +1319,37 @@ def CalculateFeatures(TckResults_multiCorr, prnList, eleList, *, ctx: Context | 
         rows.append(np.column_stack([np.full(w, float(p)), np.full(w, e)] +
                                     [getattr(f, k)[c] for k in abi.ACF_FIELDS]).reshape(w, 8))
     return np.vstack(rows)
+
+
+def scene_labels(scene, TckResults_multiCorr, prnList, *, ind_start: int = 1, numOverLap: int = 100,
+                 bytes_per_sample: int = 2):
+    """The ground truth of a synthetic scene (synth.scene_of / add_ray / set_nlos) for the feature
+    windows of CalculateFeatures: per PRN of prnList an int array with one label per window,
+      0  line of sight only,
+      1  line of sight and at least one ray of that SV present at some sample of the window,
+      2  no direct signal (los_gain == 0).
+    Window m covers the records' rows ind_start - 1 + m*numOverLap ... + numOverLap - 1, as
+    acf_features counts them. A row's samples come from absoluteSample, the file position after
+    the row's read in bytes (int8 I/Q: bytes_per_sample = 2): row i spans
+    [absoluteSample[i] - numSample[i]*bytes_per_sample, absoluteSample[i]). Host Python only."""
+    out = []
+    bps, N = int(bytes_per_sample), int(numOverLap)
+    for p in np.atleast_1d(prnList):
+        e = _struct_of(TckResults_multiCorr, p)
+        pos = np.asarray(e.absoluteSample, dtype=np.float64).ravel().astype(np.int64)
+        num = np.asarray(e.numSample, dtype=np.float64).ravel().astype(np.int64)
+        L = len(pos)
+        nwin = (L - ind_start) // N if L > ind_start else 0
+        s = synth.sv_index(scene, int(p))
+        rays = [scene.ray[r] for r in range(scene.n_ray) if scene.ray[r].sv == s and scene.ray[r].gain > 0 and scene.ray[r].t_off > scene.ray[r].t_on]
+        lab = np.zeros(nwin, dtype=np.int64)
+        for m in range(nwin):
+            r0 = ind_start - 1 + m * N
+            lo = (pos[r0] - num[r0] * bps) // bps  # first sample of the window
+            hi = pos[r0 + N - 1] // bps            # one past its last
+            if scene.los_gain[s] == 0:
+                lab[m] = 2
+            elif any(y.t_on < hi and y.t_off > lo for y in rays):
+                lab[m] = 1
+        out.append(lab)
+    return out

@@ -9,6 +9,10 @@ scenario sit at the golden acquisition result Acquired_Opensky_5000.mat
 `generate_device` fills HBM with the HIP generator (bench: multi-GB records
 without a PCIe upload); tests generate small records with the CPU twin in
 oracle/ and pass the same bytes to both paths.
+
+A scene (`scene_of`, `add_ray`, `set_nlos`) is a scenario whose SVs also carry reflected
+rays or lose their direct signal; `generate_scene_device` / `generate_scene_host` make its
+record on the GPU or the CPU, byte for byte the same, and `sdr.scene_labels` its labels.
 """
 from __future__ import annotations
 
@@ -146,6 +150,74 @@ def generate_device(ctx, cfg, dev_record, sample0=0, nsamples=None):
     ctx.check(ctx.lib.gnss_synth_if_device(ctx.h, C.byref(cfg), C.c_uint64(sample0),
                                            C.c_uint64(n), dev_record.ptr))
     return dev_record
+
+
+# ---- multipath / NLOS scenes (gnss_synth_scene; the model is in include/gnss_mi355x.h) ----
+T_FOREVER = 2 ** 64 - 1
+
+
+def scene_of(cfg) -> "abi.GnssSynthScene":
+    """A GnssSynth as a scene without rays and with every direct signal at gain 1: the same
+    record, byte for byte."""
+    sc = abi.GnssSynthScene()
+    sc.Fs, sc.IF, sc.noise_sigma, sc.seed, sc.n_sv = cfg.Fs, cfg.IF, cfg.noise_sigma, cfg.seed, cfg.n_sv
+    for i in range(abi.MAX_SV):
+        C.memmove(C.byref(sc.sv[i]), C.byref(cfg.sv[i]), C.sizeof(abi.GnssSynthSv))
+        sc.los_gain[i] = 1.0
+    sc.n_ray = 0
+    return sc
+
+
+def sv_index(scene, prn: int) -> int:
+    """The (first) SV of the scene with this PRN."""
+    for i in range(scene.n_sv):
+        if scene.sv[i].prn == int(prn):
+            return i
+    raise ValueError(f"PRN {prn} is not in the scene")
+
+
+def add_ray(scene, prn, delay_chips, gain, *, phase_cycles=0.0, fade_hz=0.0, t_on_ms=None, t_off_ms=None):
+    """One more reflected ray of PRN `prn`: its code and bits delay_chips later at `gain` times the
+    SV's unattenuated amplitude, phase_cycles and fade_hz away from the direct carrier, present
+    from t_on_ms (None: sample 0) until t_off_ms (None: forever); a millisecond is ceil(Fs*1e-3)
+    samples. Returns the ray."""
+    if scene.n_ray >= abi.MAX_RAYS:
+        raise ValueError(f"a scene holds at most {abi.MAX_RAYS} rays")
+    S = math.ceil(scene.Fs * 1e-3)
+    r = scene.ray[scene.n_ray]
+    r.sv, r.reserved = sv_index(scene, prn), 0
+    r.delay_chips, r.gain = float(delay_chips), float(gain)
+    r.phase0_cycles, r.fade_hz = float(phase_cycles), float(fade_hz)
+    r.t_on = 0 if t_on_ms is None else int(round(t_on_ms * S))
+    r.t_off = T_FOREVER if t_off_ms is None else int(round(t_off_ms * S))
+    scene.n_ray += 1
+    return r
+
+
+def set_nlos(scene, prn):
+    """PRN `prn` loses its direct signal (its rays stay)."""
+    scene.los_gain[sv_index(scene, prn)] = 0.0
+    return scene
+
+
+def generate_scene_device(ctx, scene, dev_record, sample0=0, nsamples=None):
+    """generate_device for a scene: samples [sample0, sample0+nsamples) into a DeviceRecord."""
+    n = dev_record.nbytes // 2 if nsamples is None else int(nsamples)
+    if 2 * n > dev_record.nbytes:
+        raise ValueError("the record is smaller than 2 * nsamples bytes")
+    ctx.check(ctx.lib.gnss_synth_scene_device(ctx.h, C.byref(scene), C.c_uint64(sample0), C.c_uint64(n),
+                                              dev_record.ptr))
+    return dev_record
+
+
+def generate_scene_host(scene, sample0, nsamples, nthreads=0) -> np.ndarray:
+    """The same bytes on the CPU (no context, no GPU): int8, I and Q interleaved."""
+    out = np.empty(2 * int(nsamples), dtype=np.int8)
+    st = abi.load().gnss_synth_scene_host(C.byref(scene), C.c_uint64(sample0), C.c_uint64(int(nsamples)),
+                                          out.ctypes.data_as(C.c_void_p), int(nthreads))
+    if st != abi.OK:
+        raise abi.GnssError(st, "gnss_synth_scene_host")
+    return out
 
 
 def convert_record(iq8: np.ndarray, dataPrecision: int = 1, dataType: int = 2, *, scale: int = 64,

@@ -935,6 +935,60 @@ int gnss_lnav_bits(int32_t prn, int32_t nbits, int8_t *bits_out);
 int gnss_synth_if_device(gnss_ctx *ctx, const gnss_synth *cfg, uint64_t sample0,
                          uint64_t nsamples, void *dev_dst);
 
+/* ---- synthetic IF with reflected rays (multipath / NLOS scenes) ---------- */
+/* The record of gnss_synth with, per SV, a gain on its direct signal and any number of reflected
+ * rays: the SV's own code and bit stream later in time, on a carrier of its own. Additive within
+ * ABI v13 (detected by symbol); gnss_synth and gnss_synth_if_device are as they were.
+ *
+ * Per absolute sample n and SV s (amp_s, crate_s, frate_s as gnss_synth_if_device forms them, in
+ * double on the host):
+ *   th = code_phase0 + (double)n * crate_s; chip floor(th) mod 1023; bit from
+ *   floor((th + bit_phase_chips) / 20460); ph = carr_phase0 - (double)n * frate_s, less its floor;
+ *   term (amp_s * los_gain[s]) * D * ca[chip] * (cos 2 pi ph, sin 2 pi ph).
+ * The direct terms are summed first, in SV order, then the rays in array order. Ray r of SV
+ * s = ray[r].sv is present for t_on <= n < t_off:
+ *   th_r = th - delay_chips (chip and bit from th_r by the same rules);
+ *   ph_r = (carr_phase0_s + phase0_cycles) - (double)n * frate_r, frate_r = (IF + fd + fade_hz)/Fs;
+ *   amplitude amp_s * gain.
+ * Then the noise, rounding and clipping of gnss_synth_if_device. Sample n depends on n only, and
+ * a scene without rays whose los_gain are all 1.0 is gnss_synth_if_device's record byte for byte.
+ * Simplification: a ray's delay stays constant while its phase turns (a 1 Hz fade is a path
+ * length changing by 0.19 m/s, about 6e-4 chip/s, which the model leaves out). */
+#define GNSS_MAX_RAYS 128
+typedef struct gnss_synth_ray {
+    int32_t  sv;            /* index into gnss_synth_scene.sv, 0..n_sv-1                       */
+    int32_t  reserved;
+    double   delay_chips;   /* excess path, chips (>= 0)                                       */
+    double   gain;          /* amplitude relative to the SV's unattenuated direct signal (>= 0)*/
+    double   phase0_cycles; /* carrier phase relative to the direct signal at sample 0         */
+    double   fade_hz;       /* carrier frequency relative to the direct signal                 */
+    uint64_t t_on, t_off;   /* present for t_on <= n < t_off, absolute samples                 */
+} gnss_synth_ray;
+
+typedef struct gnss_synth_scene {
+    double   Fs, IF;
+    double   noise_sigma;
+    uint64_t seed;
+    int32_t  n_sv;
+    gnss_synth_sv sv[GNSS_MAX_SV];
+    double   los_gain[GNSS_MAX_SV];  /* 1.0: gnss_synth's signal; 0.0: NLOS (rays only)         */
+    int32_t  n_ray;
+    gnss_synth_ray ray[GNSS_MAX_RAYS];  /* dealt over the SVs in any way                       */
+} gnss_synth_scene;
+
+/* gnss_synth_if_device for a scene (csrc/synth_scene.hip): fills dev_dst, this ctx's HBM (a
+ * multi-device context: devices[0]'s), and drops the members' resident copies of those bytes.
+ * GNSS_EARG, before any allocation or launch, for n_sv outside 0..GNSS_MAX_SV, n_ray outside
+ * 0..GNSS_MAX_RAYS, a PRN outside 1..51, ray.sv outside 0..n_sv-1, a negative or non-finite
+ * delay_chips, gain or los_gain, a non-finite phase0_cycles or fade_hz, and t_off < t_on. */
+int gnss_synth_scene_device(gnss_ctx *ctx, const gnss_synth_scene *scene, uint64_t sample0,
+                            uint64_t nsamples, void *dev_dst);
+
+/* The same bytes into host memory dst (2 * nsamples bytes) on nthreads CPU threads (0: up to 16).
+ * No context and no GPU; the arithmetic is the kernel's (csrc/synth_scene.h). */
+int gnss_synth_scene_host(const gnss_synth_scene *scene, uint64_t sample0, uint64_t nsamples,
+                          void *dst, int nthreads);
+
 #ifdef __cplusplus
 }
 #endif
