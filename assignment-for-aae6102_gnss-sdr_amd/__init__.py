@@ -14,12 +14,12 @@ from .sdr import (Context, DeviceRecord, DeviceTrackOutBuffers, StructArray, Tra
                   default_context, initParameters, naviDecode_updated, trackingCT, trackingCT_multiCorr,
                   trackingCT_POS, trackingCT_POS_updated_multicorrelator, trackingVT_POS_updated, trackingVT_run, trackingVT_step,
                   trackingVT_POS_updated_multicorrelator, trackingVT_mc_run, trackingVT_mc_step, vt_channel,
-                  NavSolCtBuffers, ct_positioning, findPosSV, trackingCT_POS_updated, acf_features, CalculateFeatures,
+                  NavSolCtBuffers, ct_positioning, findPosSV, trackingCT_POS_updated, acf_features, acf_fit, CalculateFeatures,
                   scene_labels)
 
 __all__ = ["abi", "synth", "Context", "DeviceRecord", "DeviceTrackOutBuffers", "StructArray", "TrackOutBuffers",
            "acquisition", "ca_code", "colon", "default_context", "initParameters", "naviDecode_updated",
            "trackingCT", "trackingCT_multiCorr", "trackingCT_POS", "trackingCT_POS_updated_multicorrelator", "trackingVT_POS_updated", "trackingVT_run", "trackingVT_step",
            "trackingVT_POS_updated_multicorrelator", "trackingVT_mc_run", "trackingVT_mc_step", "vt_channel",
-           "NavSolCtBuffers", "ct_positioning", "findPosSV", "trackingCT_POS_updated", "acf_features",
+           "NavSolCtBuffers", "ct_positioning", "findPosSV", "trackingCT_POS_updated", "acf_features", "acf_fit",
            "CalculateFeatures", "scene_labels"]

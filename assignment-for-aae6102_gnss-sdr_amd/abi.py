@@ -220,6 +220,34 @@ class GnssAcfOut(C.Structure):
 
 ADDED_STRUCTS.update({"gnss_acf_cfg": "GnssAcfCfg", "gnss_acf_out": "GnssAcfOut"})
 
+# The two-path fit of the 25-tap ACF (gnss_acf_fit / gnss_acf_fit_window; additive within ABI
+# v13): the windows' parameters as above, the grid and the two thresholds; `orient` has no
+# default (the 25-tap loops' wrappers tag their results with it: ACF_ORIENT)
+ACF_FIT_DEFAULTS = dict(ind_start=1, numOverLap=100, corrSpacing=0.05, p_min=-0.40, p_step=0.01, p_count=81,
+                        e_min=0.05, e_step=0.01, e_count=96, ratio_max=1.0, gain_min=16.0)
+ACF_FIT_FIELDS = ["bias", "p1", "A1p_re", "A1p_im", "res1", "p0", "e", "A0_re", "A0_im", "A1_re", "A1_im", "res2",
+                  "energy"]
+# u[j] = orient * (j - 12) * corrSpacing is the loop's Spacing(j): -0.6:0.05:0.6 in
+# trackingCT_multiCorr-GIVEN.m:25, 0.6:-0.05:-0.6 in the two _multicorrelator loops
+ACF_ORIENT = dict(trackingCT_multiCorr=1, trackingCT_POS_updated_multicorrelator=-1,
+                  trackingVT_POS_updated_multicorrelator=-1)
+
+
+class GnssAcfFitCfg(C.Structure):
+    _fields_ = [("n", C.c_int32), ("ind_start", C.c_int32), ("numOverLap", C.c_int32), ("orient", C.c_int32),
+                ("corrSpacing", C.c_double), ("p_min", C.c_double), ("p_step", C.c_double), ("e_min", C.c_double),
+                ("e_step", C.c_double), ("p_count", C.c_int32), ("e_count", C.c_int32), ("ratio_max", C.c_double),
+                ("gain_min", C.c_double)]
+
+
+class GnssAcfFitOut(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("windows", C.POINTER(C.c_int64)), ("paths", C.POINTER(C.c_int32))] + \
+               [(f, C.POINTER(C.c_double)) for f in ACF_FIT_FIELDS] + \
+               [("zI", C.POINTER(C.c_double)), ("zQ", C.POINTER(C.c_double))]
+
+
+ADDED_STRUCTS.update({"gnss_acf_fit_cfg": "GnssAcfFitCfg", "gnss_acf_fit_out": "GnssAcfFitOut"})
+
 
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
@@ -347,6 +375,11 @@ PROTOTYPES = {
     # ACF/CalculateFeatures.m over the 25-tap records (additive within ABI v13: detected by symbol)
     "gnss_acf_features": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfCfg), C.POINTER(GnssTrackOut), C.c_int32,
                                     C.POINTER(GnssAcfOut)]),
+    # the two-path fit of the 25-tap ACF (additive within ABI v13: detected by symbol)
+    "gnss_acf_fit": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfFitCfg), C.POINTER(GnssTrackOut), C.c_int32,
+                               C.POINTER(GnssAcfFitOut)]),
+    "gnss_acf_fit_window": (C.c_int, [C.POINTER(GnssAcfFitCfg), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(GnssAcfFitOut)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

@@ -538,12 +538,15 @@ def trackingCT_POS_updated_multicorrelator(file, signal, track, Acquired, *,
     st = ctx.lib.gnss_tracking_ct_mc(ctx.h, C.byref(f), C.byref(s), C.byref(t), C.byref(a),
                                      msPosCT, pdi, C.byref(buf.c))
     ctx.check(st)
+    buf.acf_orient = abi.ACF_ORIENT["trackingCT_POS_updated_multicorrelator"]  # (acf_fit reads it)
     if raw:
         return buf
     if device_records:
         buf = buf.host()
     cn0 = buf.CN0[: buf.c.cn0_rows].copy()
-    return mc_result(Acquired, buf, channels), cn0
+    res = mc_result(Acquired, buf, channels)
+    res.acf_orient = buf.acf_orient
+    return res, cn0
 
 
 def trackingCT_multiCorr(file, signal, track, Acquired, *, datalength: int = 50000,
@@ -567,9 +570,12 @@ def trackingCT_multiCorr(file, signal, track, Acquired, *, datalength: int = 500
     st = ctx.lib.gnss_tracking_ct_multicorr(ctx.h, C.byref(f), C.byref(s), C.byref(t), C.byref(a),
                                             int(datalength), C.byref(buf.c))
     ctx.check(st)
+    buf.acf_orient = abi.ACF_ORIENT["trackingCT_multiCorr"]  # (acf_fit reads it)
     if raw:
         return buf
-    return mc_result(Acquired, buf, None, abi.FIELDS), buf.CN0[: buf.c.cn0_rows].copy()
+    res = mc_result(Acquired, buf, None, abi.FIELDS)
+    res.acf_orient = buf.acf_orient
+    return res, buf.CN0[: buf.c.cn0_rows].copy()
 
 
 def naviDecode_updated(Acquired, ALLTckResult, *, eph_cap: int = 512):
@@ -1001,6 +1007,7 @@ def trackingVT_POS_updated_multicorrelator(file, signal, track, cmn, solu, Acqui
         entries[p] = e
     nsol = _navsol_arrays(sols, nsteps, n)
     res = StructArray(entries)
+    res.acf_orient = abi.ACF_ORIENT["trackingVT_POS_updated_multicorrelator"]  # (acf_fit reads it)
     if return_cn0:
         return res, nsol, _cn0_rows(R, nsteps, n)
     return res, nsol
@@ -1213,6 +1220,35 @@ def _acf_pack(TckResults_multiCorr, prnList):
     return o, (rec, taps, lens)
 
 
+def _acf_records(records, prn, ctx, who):
+    """The gnss_track_out a pass over 25-tap records reads, for the raw TrackOutBuffers of a loop
+    (host or device) or the per-PRN structs: (rec, what keeps its arrays alive, lens, max_len,
+    on_device, ctx)."""
+    n = len(prn)
+    on_device = isinstance(records, DeviceTrackOutBuffers)
+    if isinstance(records, TrackOutBuffers):
+        if records.taps is None or records.taps.shape[2] != abi.MC_TAPS or records.taps.shape[0] < n:
+            raise ValueError(f"{who}: the records of a 25-tap loop, one channel per PRN")
+        lens, max_len = records.len, records.max_len
+        if on_device:
+            rec, keep = records.c, records
+            ctx = ctx or default_context()
+            records.sync_producer()
+        else:  # (a host copy of device buffers still carries their gnss_track_out: build it anew)
+            keep = (np.ascontiguousarray(records.rec, dtype=np.float64),
+                    np.ascontiguousarray(records.taps, dtype=np.float64),
+                    np.ascontiguousarray(records.len, dtype=np.int64))
+            rec = abi.GnssTrackOut()
+            rec.max_len = max_len
+            rec.rec = keep[0].ctypes.data_as(C.POINTER(C.c_double))
+            rec.taps = keep[1].ctypes.data_as(C.POINTER(C.c_double))
+            rec.len = keep[2].ctypes.data_as(C.POINTER(C.c_int64))
+    else:
+        rec, keep = _acf_pack(records, prn)
+        lens, max_len = keep[2], rec.max_len
+    return rec, keep, lens, max_len, on_device, ctx
+
+
 def acf_features(records, prnList, eleList, *, ctx: Context | None = None, want_index: bool = False,
                  want_corr: bool = False, **params):
     """The features of ACF/CalculateFeatures.m per channel (gnss_acf_features): a namespace of
@@ -1238,27 +1274,7 @@ def acf_features(records, prnList, eleList, *, ctx: Context | None = None, want_
         raise ValueError("prnList and eleList differ in length")
     if n > abi.VT_MAX_CH:
         raise ValueError(f"acf_features takes at most {abi.VT_MAX_CH} channels")
-    on_device = isinstance(records, DeviceTrackOutBuffers)
-    if isinstance(records, TrackOutBuffers):
-        if records.taps is None or records.taps.shape[2] != abi.MC_TAPS or records.taps.shape[0] < n:
-            raise ValueError("acf_features: the records of a 25-tap loop, one channel per PRN")
-        lens, max_len = records.len, records.max_len
-        if on_device:
-            rec, keep = records.c, records
-            ctx = ctx or default_context()
-            records.sync_producer()
-        else:  # (a host copy of device buffers still carries their gnss_track_out: build it anew)
-            keep = (np.ascontiguousarray(records.rec, dtype=np.float64),
-                    np.ascontiguousarray(records.taps, dtype=np.float64),
-                    np.ascontiguousarray(records.len, dtype=np.int64))
-            rec = abi.GnssTrackOut()
-            rec.max_len = max_len
-            rec.rec = keep[0].ctypes.data_as(C.POINTER(C.c_double))
-            rec.taps = keep[1].ctypes.data_as(C.POINTER(C.c_double))
-            rec.len = keep[2].ctypes.data_as(C.POINTER(C.c_int64))
-    else:
-        rec, keep = _acf_pack(records, prn)
-        lens, max_len = keep[2], rec.max_len
+    rec, keep, lens, max_len, on_device, ctx = _acf_records(records, prn, ctx, "acf_features")
     cfg = abi.GnssAcfCfg()
     cfg.n, cfg.ind_start, cfg.numOverLap = n, int(par["ind_start"]), int(par["numOverLap"])
     cfg.corrSpacing, cfg.maxDelay = float(par["corrSpacing"]), float(par["maxDelay"])
@@ -1319,6 +1335,82 @@ def CalculateFeatures(TckResults_multiCorr, prnList, eleList, *, ctx: Context | 
         rows.append(np.column_stack([np.full(w, float(p)), np.full(w, e)] +
                                     [getattr(f, k)[c] for k in abi.ACF_FIELDS]).reshape(w, 8))
     return np.vstack(rows)
+
+
+def acf_fit(records, prnList, *, ctx: Context | None = None, want_acf: bool = False, **params):
+    """The two-path fit of the 25-tap ACF per feature window (gnss_acf_fit): a direct path plus
+    one reflected path fitted to the window's coherently summed correlation function. A namespace
+    of prn, windows [n] and, per name below, a list of n arrays with one value per window (the
+    windows are acf_features': row m lines up with feature row m and label m):
+      paths     2: the two-path model is selected, 1: one path, 0: no fit (a non-finite sum)
+      bias      chips the prompt is late against the direct path (subtract it from the code
+                delay); bias_m the same in metres, bias * cSpeed / codeFreqBasis
+      p1, A1p_re, A1p_im, res1                     the one-path fit
+      p0, e, A0_re, A0_im, A1_re, A1_im, res2      the two-path fit: the direct path at p0, the
+                reflected one e chips later (NaN where no two-path hypothesis survived)
+      ratio     |A1| / |A0|;  dphi_cycles  the reflected path's carrier phase against the direct
+                path's, cycles in (-0.5, 0.5]
+      energy    of the coherent vector; with want_acf also zI, zQ [25][windows] per channel.
+
+    `records` as for acf_features; DeviceTrackOutBuffers are read where they lie by the kernel,
+    host records need no GPU. params: orient (+1 / -1: which way the loop's Spacing runs over the
+    stored taps; the three 25-tap loops tag what they return with it as .acf_orient, so it is
+    needed only for records from elsewhere), ind_start, numOverLap, corrSpacing, the grid p_min,
+    p_step, p_count, e_min, e_step, e_count, and ratio_max, gain_min (abi.ACF_FIT_DEFAULTS);
+    cSpeed and codeFreqBasis for bias_m.
+    """
+    cSpeed = float(params.pop("cSpeed", 299792458.0))
+    codeFreqBasis = float(params.pop("codeFreqBasis", 1.023e6))
+    orient = params.pop("orient", getattr(records, "acf_orient", None))
+    if orient is None:
+        raise ValueError("acf_fit: orient (+1 or -1) is needed for records that no 25-tap loop tagged")
+    unknown = set(params) - set(abi.ACF_FIT_DEFAULTS)
+    if unknown:
+        raise TypeError(f"acf_fit: unknown parameter(s) {sorted(unknown)}")
+    par = dict(abi.ACF_FIT_DEFAULTS, **params)
+    prn = [int(p) for p in np.atleast_1d(prnList)]
+    n = len(prn)
+    if n > abi.VT_MAX_CH:
+        raise ValueError(f"acf_fit takes at most {abi.VT_MAX_CH} channels")
+    rec, keep, lens, max_len, on_device, ctx = _acf_records(records, prn, ctx, "acf_fit")
+    cfg = abi.GnssAcfFitCfg()
+    cfg.n, cfg.orient = n, int(orient)
+    for k in ("ind_start", "numOverLap", "p_count", "e_count"):
+        setattr(cfg, k, int(par[k]))
+    for k in ("corrSpacing", "p_min", "p_step", "e_min", "e_step", "ratio_max", "gain_min"):
+        setattr(cfg, k, float(par[k]))
+    nov = max(cfg.numOverLap, 1)
+    cap = max([max(int(l) - cfg.ind_start, 0) // nov for l in lens[:n]] + [1])
+    out = abi.GnssAcfFitOut()
+    out.cap = cap
+    windows = np.zeros(max(n, 1), dtype=np.int64)
+    out.windows = windows.ctypes.data_as(C.POINTER(C.c_int64))
+    paths = np.zeros((max(n, 1), cap), dtype=np.int32)
+    out.paths = paths.ctypes.data_as(C.POINTER(C.c_int32))
+    arr = {f: np.zeros((max(n, 1), cap)) for f in abi.ACF_FIT_FIELDS}
+    if want_acf:
+        arr["zI"], arr["zQ"] = np.zeros((max(n, 1), abi.MC_TAPS, cap)), np.zeros((max(n, 1), abi.MC_TAPS, cap))
+    for f, a in arr.items():
+        setattr(out, f, a.ctypes.data_as(C.POINTER(C.c_double)))
+    lib = abi.load()
+    h = ctx.h if ctx is not None else None
+    st = lib.gnss_acf_fit(h, C.byref(cfg), C.byref(rec), abi.MC_TAPS, C.byref(out))
+    if st != abi.OK:
+        msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
+        raise abi.GnssError(st, msg)
+    res = SimpleNamespace(prn=prn, windows=windows[:n].copy(), orient=int(orient),
+                          paths=[paths[c, : windows[c]].copy() for c in range(n)])
+    for f, a in arr.items():
+        setattr(res, f, [a[c, ..., : windows[c]].copy() for c in range(n)])
+    res.bias_m, res.ratio, res.dphi_cycles = [], [], []
+    for c in range(n):
+        a0 = res.A0_re[c] + 1j * res.A0_im[c]
+        a1 = res.A1_re[c] + 1j * res.A1_im[c]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            res.bias_m.append(res.bias[c] * cSpeed / codeFreqBasis)
+            res.ratio.append(np.abs(a1) / np.abs(a0))
+            res.dphi_cycles.append(np.angle(a1 * np.conj(a0)) / (2 * np.pi))
+    return res
 
 
 def scene_labels(scene, TckResults_multiCorr, prnList, *, ind_start: int = 1, numOverLap: int = 100,

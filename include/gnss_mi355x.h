@@ -899,6 +899,79 @@ typedef struct gnss_acf_out {
 int gnss_acf_features(gnss_ctx *ctx, const gnss_acf_cfg *cfg, const gnss_track_out *records,
                       int32_t n_taps, gnss_acf_out *out);
 
+/* ---- two-path fit of the 25-tap ACF (additive within ABI v13; detected by symbol) ---------
+ * A multipath delay estimate per feature window: a direct path plus one reflected path fitted to
+ * the coherently summed 25-tap correlation function. It goes beyond the reference, which has no
+ * such estimator. All arithmetic fp64, every operation rounded on its own, every sum left to
+ * right from its first term (csrc/acf_fit.h is the one source for host and device).
+ *   - Windows: gnss_acf_features' (ind_start, numOverLap, the same count and rows), so fit row m
+ *     of channel c lines up with feature row m.
+ *   - Coherent vector: for row r of the window s_r = +1 if the prompt's I sum (tap 12 of 0..24) is
+ *     >= 0, else -1 (a NaN gives -1); zI[j] = sum_r s_r*I[j][r], zQ[j] = sum_r s_r*Q[j][r], rows
+ *     ascending; energy = sum_j (zI[j]*zI[j] + zQ[j]*zQ[j]).
+ *   - Tap coordinate u[j] = (orient * (j - 12)) * corrSpacing. With orient = +1 a path that
+ *     arrives later sits at a lower u (the records of gnss_tracking_ct_multicorr); the 10-ms
+ *     loop of gnss_tracking_ct_mc and the vector loop store their taps the other way: -1.
+ *   - Model R(x) = max(0, 1 - |x|). Grid p = p_min + ip*p_step, e = e_min + ie*e_step.
+ *   - One path, per ip with r_j = R(u[j] - p): a = sum r_j*r_j (skipped if a == 0),
+ *     A = (sum r_j*z_j) / a per component, res = sum_j |z_j - A*r_j|^2 as dI*dI + dQ*dQ. The
+ *     smallest res wins, the lowest ip on a tie; a NaN res never wins.
+ *   - Two paths, h = ip*e_count + ie, r0_j = R(u[j] - p), r1_j = R(u[j] - (p - e)): a = sum r0*r0,
+ *     b = sum r1*r1, c = sum r0*r1, h0 = sum r0*z, h1 = sum r1*z, det = a*b - c*c; skipped if
+ *     a == 0, b == 0 or !(det > (1e-9*a)*b) (a path outside the tap span);
+ *     A0 = (b*h0 - c*h1)/det, A1 = (a*h1 - c*h0)/det; skipped if |A1|^2 > (ratio_max*ratio_max) *
+ *     |A0|^2 (a reflection above the direct path is the NLOS case and belongs to the one-path
+ *     fit); res = sum_j |(z_j - A0*r0_j) - A1*r1_j|^2. The smallest (res, h) wins.
+ *   - paths = 2 iff a two-path hypothesis survived and res1 > gain_min*res2, else 1; paths = 0
+ *     (every output of the window NaN) for a non-finite z or when no one-path hypothesis
+ *     survived. bias = p of the selected model, chips: how late the prompt is against the direct
+ *     path. A0 is the direct path, A1 the reflected one, e > 0 its excess delay in chips. */
+typedef struct gnss_acf_fit_cfg {
+    int32_t n;                  /* channels: the first n of the record set, 1..GNSS_VT_MAX_CH */
+    int32_t ind_start;          /* as gnss_acf_cfg; default 1                                 */
+    int32_t numOverLap;         /* rows per window, 2..4096; default 100                      */
+    int32_t orient;             /* +1 or -1 (above)                                           */
+    double  corrSpacing;        /* default 0.05                                               */
+    double  p_min, p_step;      /* default -0.40, 0.01                                        */
+    double  e_min, e_step;      /* default 0.05, 0.01                                         */
+    int32_t p_count, e_count;   /* default 81, 96; each >= 1, p_count*e_count <= 65536        */
+    double  ratio_max;          /* default 1.0                                                */
+    double  gain_min;           /* default 16.0                                               */
+} gnss_acf_fit_cfg;
+
+/* Caller-allocated host arrays, row-major [n][cap]: channel c's window m (0-based) is at
+ * [c * cap + m], windows[c] of them written. zI and zQ are optional (NULL: not wanted):
+ * [(c * 25 + j) * cap + m] is tap j of the window's coherent vector. */
+typedef struct gnss_acf_fit_out {
+    int64_t  cap;             /* windows per channel the arrays hold                          */
+    int64_t *windows;         /* [n]                                                          */
+    int32_t *paths;           /* 0, 1 or 2                                                    */
+    double  *bias;            /* chips                                                        */
+    double  *p1, *A1p_re, *A1p_im, *res1;                       /* the one-path fit           */
+    double  *p0, *e, *A0_re, *A0_im, *A1_re, *A1_im, *res2;     /* the two-path fit, or NaN   */
+    double  *energy;
+    double  *zI, *zQ;         /* [n][25][cap]; may be NULL                                    */
+} gnss_acf_fit_out;
+
+/* The fit over a record set. records: taps [nsv][2][25][max_len], len, max_len and flags are
+ * read; n_taps must be GNSS_MC_TAPS. Host records need no GPU and ctx may be NULL (up to 16
+ * threads); with GNSS_OUT_DEVICE taps is a device pointer of the context's device and the fit
+ * runs on the GPU (csrc/acf_fit.hip), one block per window. Both paths give the same bits in
+ * every output. Device records on a context of gnss_ctx_create_multi return GNSS_EARG. GNSS_EARG
+ * also for n_taps != 25, n outside 1..GNSS_VT_MAX_CH, numOverLap outside 2..4096, ind_start < 1,
+ * orient not +-1, corrSpacing, p_step or e_step not positive, a non-finite p_min or e_min, a count
+ * below 1, p_count*e_count > 65536, a ratio_max or gain_min that is negative or NaN, len[c]
+ * outside 0..max_len and more windows than cap: all checked on the host before any launch. */
+int gnss_acf_fit(gnss_ctx *ctx, const gnss_acf_fit_cfg *cfg, const gnss_track_out *records,
+                 int32_t n_taps, gnss_acf_fit_out *out);
+
+/* The fit alone on one coherent vector zI[25], zQ[25], host only: cfg's orient, corrSpacing, grid
+ * and thresholds are read (n, ind_start and numOverLap are not); out is a gnss_acf_fit_out with
+ * cap >= 1 whose element [0] of every array is written (windows[0] = 1; zI / zQ, if given, get
+ * the vector at [j * cap]). For known-answer tests and for a caller that forms z differently. */
+int gnss_acf_fit_window(const gnss_acf_fit_cfg *cfg, const double *zI, const double *zQ,
+                        gnss_acf_fit_out *out);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
