@@ -220,6 +220,24 @@ class GnssAcfOut(C.Structure):
 
 ADDED_STRUCTS.update({"gnss_acf_cfg": "GnssAcfCfg", "gnss_acf_out": "GnssAcfOut"})
 
+# The script's F6-F8 (gnss_acf_features_ext; additive within ABI v13): the history's length (:231),
+# the spectrum's (:264) and the departure on offer; fs has no default here, it follows from
+# numOverLap and pdi (:172). The outputs in the 11-column data_labeled's order (:32).
+ACF_EXT_DEFAULTS = dict(fft_hist=300, fft_n=1024, fft_fill=0)
+ACF_EXT_FIELDS = ("numMLC", "fftFreq", "fftMag")
+
+
+class GnssAcfExtCfg(C.Structure):
+    _fields_ = [("fft_hist", C.c_int32), ("fft_n", C.c_int32), ("fft_fill", C.c_int32), ("reserved", C.c_int32),
+                ("fs", C.c_double)]
+
+
+class GnssAcfExtOut(C.Structure):
+    _fields_ = [(f, C.POINTER(C.c_double)) for f in ACF_EXT_FIELDS]
+
+
+ADDED_STRUCTS.update({"gnss_acf_ext_cfg": "GnssAcfExtCfg", "gnss_acf_ext_out": "GnssAcfExtOut"})
+
 # The two-path fit of the 25-tap ACF (gnss_acf_fit / gnss_acf_fit_window; additive within ABI
 # v13): the windows' parameters as above, the grid and the two thresholds; `orient` has no
 # default (the 25-tap loops' wrappers tag their results with it: ACF_ORIENT)
@@ -375,6 +393,10 @@ PROTOTYPES = {
     # ACF/CalculateFeatures.m over the 25-tap records (additive within ABI v13: detected by symbol)
     "gnss_acf_features": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfCfg), C.POINTER(GnssTrackOut), C.c_int32,
                                     C.POINTER(GnssAcfOut)]),
+    "gnss_acf_features_ext": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfCfg), C.POINTER(GnssAcfExtCfg),
+                                        C.POINTER(GnssTrackOut), C.c_int32, C.POINTER(GnssAcfOut),
+                                        C.POINTER(GnssAcfExtOut)]),
+    "gnss_acf_twiddle": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # the two-path fit of the 25-tap ACF (additive within ABI v13: detected by symbol)
     "gnss_acf_fit": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfFitCfg), C.POINTER(GnssTrackOut), C.c_int32,
                                C.POINTER(GnssAcfFitOut)]),

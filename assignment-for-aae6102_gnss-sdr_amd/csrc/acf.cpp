@@ -2,11 +2,14 @@
 // definition is in include/gnss_mi355x.h, the arithmetic in acf.h). The argument and bound
 // checks, the host path (acf.h's functions in loops) and, for GNSS_OUT_DEVICE records, the
 // scratch, the launches of acf.hip and the features' download. F1 and expectedCorr are computed
-// here on both paths. Built with -ffp-contract=off: every operation rounds on its own.
+// here on both paths. gnss_acf_features_ext (acf_ext.cpp) runs the same pass with the row pass
+// counting acf_ext.h's local maxima as well. Built with -ffp-contract=off: every operation
+// rounds on its own.
 #include <cmath>
 #include <cstring>
 
 #include "acf.h"
+#include "acf_ext.h"
 #include "host.h"
 
 using namespace gnss;
@@ -35,12 +38,14 @@ void store_window(const gnss_acf_cfg& cfg, gnss_acf_out* out, int c, int64_t m, 
 }
 
 // one channel on the host: the row pass a tap at a time (each series is contiguous), then the
-// windows
-void host_channel(const gnss_acf_cfg& cfg, const gnss_track_out& r, gnss_acf_out* out, int c, double cenDelay)
+// windows; with `ext` the rows' local-maximum counts beside the arg-max, and F6-F8 after the windows
+void host_channel(const gnss_acf_cfg& cfg, const gnss_track_out& r, gnss_acf_out* out, int c, double cenDelay,
+                  const AcfExtPlan* ext)
 {
     const int64_t L = r.len[c], ml = r.max_len;
     std::vector<double> pm((size_t)L);
     std::vector<AcfPeak> peak((size_t)L);
+    std::vector<AcfMlc> mlc(ext ? (size_t)L : 0);
     std::vector<uint8_t> idx_own;
     uint8_t* idx = out->maxCorrInd ? out->maxCorrInd + (int64_t)c * ml : nullptr;
     if (!idx) {
@@ -56,6 +61,7 @@ void host_channel(const gnss_acf_cfg& cfg, const gnss_track_out& r, gnss_acf_out
             acf_peak_take(peak[i], m, j + 1);
             if (j == kAcfPrompt) pm[i] = m;
             if (corr) corr[i] = m;
+            if (ext) acf_mlc_take(mlc[i], m);
         }
     }
     for (int64_t i = 0; i < L; i++) idx[i] = (uint8_t)peak[i].idx;
@@ -66,14 +72,18 @@ void host_channel(const gnss_acf_cfg& cfg, const gnss_track_out& r, gnss_acf_out
                      acf_window(pm.data() + row, idx + row, disc + row, cfg.numOverLap, m == 0, cfg.corrSpacing,
                                 cenDelay));
     }
+    if (ext) {
+        std::vector<uint8_t> cnt((size_t)L);
+        for (int64_t i = 0; i < L; i++) cnt[i] = (uint8_t)mlc[i].cnt;
+        acf_ext_host_channel(*ext, c, out->cap, out->windows[c], cfg.ind_start, cfg.numOverLap, cnt.data(),
+                             out->meanMax + (int64_t)c * out->cap);
+    }
 }
 
 }  // namespace
 
-extern "C" {
-
-int gnss_acf_features(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_out* rec, int32_t n_taps,
-                      gnss_acf_out* out)
+int gnss::host::acf_features_run(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_out* rec, int32_t n_taps,
+                                 gnss_acf_out* out, const AcfExtPlan* ext)
 {
     if (!cfg || !rec || !out) return fail(ctx, GNSS_EARG, "gnss_acf_features: a null argument");
     const int n = cfg->n;
@@ -102,6 +112,8 @@ int gnss_acf_features(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_o
                         (long long)d.windows[c]);
         d.win_base[c + 1] = d.win_base[c] + d.windows[c];
     }
+    if (ext && d.win_base[n] > 0x7fffffff)  // (acf_spectrum_kernel: one block per window)
+        return fail(ctx, GNSS_EARG, "gnss_acf_features_ext: more than 2^31 - 1 windows");
     const bool on_device = (rec->flags & GNSS_OUT_DEVICE) != 0;
     if (on_device) {
         if (!ctx) return GNSS_EARG;
@@ -111,16 +123,17 @@ int gnss_acf_features(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_o
     const double cenDelay = acf_cen_delay(cfg->maxDelay, cfg->corrSpacing);
     for (int c = 0; c < n; c++) out->windows[c] = d.windows[c];
     if (!on_device) {
-        parallel_for(n, [&](int c) { host_channel(*cfg, *rec, out, c, cenDelay); });
+        parallel_for(n, [&](int c) { host_channel(*cfg, *rec, out, c, cenDelay, ext); });
         return GNSS_OK;
     }
 
     HIP_TRY(hipSetDevice(ctx->device));
     const int64_t ml = rec->max_len, total = d.win_base[n];
-    DevBuf pm, idx, feat;
+    DevBuf pm, idx, feat, cnt;
     HIP_TRY(pm.alloc(ctx, "acf_pm", (size_t)n * ml * sizeof(double)));
     if (!out->maxCorrInd) HIP_TRY(idx.alloc(ctx, "acf_idx", (size_t)n * ml));
     HIP_TRY(feat.alloc(ctx, "acf_feat", (size_t)5 * total * sizeof(double)));
+    if (ext) HIP_TRY(cnt.alloc(ctx, "acf_cnt", (size_t)n * ml));
     d.taps = rec->taps;
     d.rec = rec->rec;
     d.max_len = ml;
@@ -135,6 +148,7 @@ int gnss_acf_features(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_o
     d.idx = out->maxCorrInd ? out->maxCorrInd : idx.as<uint8_t>();
     d.corr = out->corr;
     d.feat = feat.as<double>();
+    d.cnt = ext ? cnt.as<uint8_t>() : nullptr;
     auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const bool vec2 = ml % 2 == 0 && aligned16(d.taps) && aligned16(d.pm) && aligned16(d.corr);
     const int le = acf_launch(d, vec2, ctx->stream);
@@ -146,6 +160,8 @@ int gnss_acf_features(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_o
         if (!h) return fail(ctx, GNSS_EDEVICE, "gnss_acf_features: pinned staging");
         HIP_TRY(hipMemcpyAsync(h, d.feat, (size_t)5 * total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }
+    if (ext)
+        if (const int st = acf_ext_device(ctx, *ext, d, out->cap)) return st;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int c = 0; c < n; c++)
         for (int64_t m = 0; m < d.windows[c]; m++) {
@@ -154,6 +170,14 @@ int gnss_acf_features(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_o
                          AcfWindow{h[w], h[total + w], h[2 * total + w], h[3 * total + w], h[4 * total + w]});
         }
     return GNSS_OK;
+}
+
+extern "C" {
+
+int gnss_acf_features(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_out* rec, int32_t n_taps,
+                      gnss_acf_out* out)
+{
+    return acf_features_run(ctx, cfg, rec, n_taps, out, nullptr);
 }
 
 }  // extern "C"

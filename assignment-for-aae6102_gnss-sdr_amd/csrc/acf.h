@@ -122,6 +122,7 @@ struct AcfDev {
     uint8_t* idx;     // [n][max_len] arg-max indices
     double* corr;     // [n][25][max_len] or null
     double* feat;     // [5][win_base[n]]: meanMax, meanDelay, varDelay, meanCodeDisc, varCodeDisc
+    uint8_t* cnt;     // [n][max_len] interior local maxima per row (acf_ext.h), or null: not wanted
 };
 
 // The two launches on `stream` (a hipStream_t) of the current device: the row pass over

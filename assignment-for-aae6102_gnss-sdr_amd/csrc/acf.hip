@@ -9,7 +9,8 @@
 //                         the first use, forms the magnitudes and carries the first-index
 //                         arg-max; it writes the prompt magnitude (8 B) and the index (1 B) per
 //                         row and, if asked for, the 25 magnitudes. Every tap value is read from
-//                         HBM exactly once.
+//                         HBM exactly once. For gnss_acf_features_ext the same pass also counts
+//                         the row's interior local maxima (acf_ext.h) into one more byte.
 //   2. acf_window_kernel  one lane per window over those compact per-row values and the code
 //                         discriminator's series, summing left to right as the host does.
 // The arithmetic is acf.h's, shared with the host path, without contraction (and no fast-math
@@ -19,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "acf.h"
+#include "acf_ext.h"
 
 namespace gnss {
 namespace {
@@ -41,8 +43,10 @@ template <> struct RowVec<2> {
 
 // rows [i, i + VEC) of channel blockIdx.y, i < len (the host checked len <= max_len; with VEC = 2
 // max_len is even and i is even, so row i + 1 < max_len is inside every series even when it is
-// past len: it is loaded, never stored)
-template <int VEC, bool CORR>
+// past len: it is loaded, never stored). MLC (gnss_acf_features_ext): the lane also carries
+// acf_ext.h's local-maximum counter, two magnitudes per row across the groups, and writes one
+// more byte per row; without it the kernel is the one gnss_acf_features always had.
+template <int VEC, bool CORR, bool MLC>
 __global__ __launch_bounds__(kRowThreads) void acf_row_kernel(AcfDev d)
 {
     using V = typename RowVec<VEC>::type;
@@ -54,6 +58,7 @@ __global__ __launch_bounds__(kRowThreads) void acf_row_kernel(AcfDev d)
     const int64_t q_off = (int64_t)kAcfTaps * d.max_len;
     AcfPeak peak[VEC];
     double prompt[VEC] = {};
+    AcfMlc mlc[VEC];
     // (the group loop stays rolled: unrolled, the compiler hoists all 50 loads to the top, 200
     // VGPRs at two rows per lane, and spills under any occupancy bound)
 #pragma unroll 1
@@ -74,6 +79,7 @@ __global__ __launch_bounds__(kRowThreads) void acf_row_kernel(AcfDev d)
                 m[e] = acf_mag(RowVec<VEC>::at(I[k], e), RowVec<VEC>::at(Q[k], e));
                 acf_peak_take(peak[e], m[e], j + 1);
                 if (j == kAcfPrompt) prompt[e] = m[e];
+                if (MLC) acf_mlc_take(mlc[e], m[e]);
             }
             if (CORR) {
                 double* o = d.corr + ((int64_t)c * kAcfTaps + j) * d.max_len + i;
@@ -96,10 +102,24 @@ __global__ __launch_bounds__(kRowThreads) void acf_row_kernel(AcfDev d)
         *reinterpret_cast<double2_t*>(d.pm + r) = v;
         d.idx[r] = (uint8_t)peak[0].idx;
         d.idx[r + 1] = (uint8_t)peak[VEC - 1].idx;
+        if (MLC) {
+            d.cnt[r] = (uint8_t)mlc[0].cnt;
+            d.cnt[r + 1] = (uint8_t)mlc[VEC - 1].cnt;
+        }
     } else {
         d.pm[r] = prompt[0];
         d.idx[r] = (uint8_t)peak[0].idx;
+        if (MLC) d.cnt[r] = (uint8_t)mlc[0].cnt;
     }
+}
+
+template <int VEC, bool CORR>
+void launch_rows(const AcfDev& d, dim3 grid, hipStream_t stream)
+{
+    if (d.cnt)
+        hipLaunchKernelGGL((acf_row_kernel<VEC, CORR, true>), grid, dim3(kRowThreads), 0, stream, d);
+    else
+        hipLaunchKernelGGL((acf_row_kernel<VEC, CORR, false>), grid, dim3(kRowThreads), 0, stream, d);
 }
 
 // window w of all channels' windows in channel order; its rows lie below len[c] (host check)
@@ -133,13 +153,13 @@ int acf_launch(const AcfDev& d, bool vec2, void* stream_)
         const int per_block = kRowThreads * (vec2 ? 2 : 1);
         const dim3 grid((unsigned)((rows + per_block - 1) / per_block), (unsigned)d.n);
         if (vec2 && d.corr)
-            hipLaunchKernelGGL((acf_row_kernel<2, true>), grid, dim3(kRowThreads), 0, stream, d);
+            launch_rows<2, true>(d, grid, stream);
         else if (vec2)
-            hipLaunchKernelGGL((acf_row_kernel<2, false>), grid, dim3(kRowThreads), 0, stream, d);
+            launch_rows<2, false>(d, grid, stream);
         else if (d.corr)
-            hipLaunchKernelGGL((acf_row_kernel<1, true>), grid, dim3(kRowThreads), 0, stream, d);
+            launch_rows<1, true>(d, grid, stream);
         else
-            hipLaunchKernelGGL((acf_row_kernel<1, false>), grid, dim3(kRowThreads), 0, stream, d);
+            launch_rows<1, false>(d, grid, stream);
     }
     const int64_t total = d.win_base[d.n];
     if (total > 0)

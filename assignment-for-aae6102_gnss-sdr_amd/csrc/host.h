@@ -53,6 +53,8 @@ struct gnss_ctx {
 };
 
 namespace gnss {
+struct AcfDev;      // acf.h
+struct AcfExtPlan;  // acf_ext.h
 namespace host {
 
 // Timing-probe hooks read from the environment in probe builds only (tools/build_probe.sh
@@ -201,6 +203,19 @@ void ca_bits(int prn, unsigned* out32);
 // The sampling-rate floor of the tracking kernels (api_track.cpp)
 bool lane_rate_admitted(const gnss_signal* sg, double codeFreq_max);
 int refuse_lane_rate(gnss_ctx* ctx, const gnss_signal* sg, double codeFreq_max);
+
+// (acf.cpp) gnss_acf_features' pass. ext == nullptr: that call as it is; otherwise the pass of
+// gnss_acf_features_ext (acf_ext.cpp, which checked *ext): the row pass also counts the local
+// maxima and the windows' F6-F8 go to ext's arrays, `out` being the same bits either way.
+int acf_features_run(gnss_ctx* ctx, const gnss_acf_cfg* cfg, const gnss_track_out* rec, int32_t n_taps,
+                     gnss_acf_out* out, const AcfExtPlan* ext);
+// (acf_ext.cpp) the host path's F6-F8 of channel c: cnt [len] the rows' counts, meanMax the
+// channel's `windows` values, the outputs at [c * cap + m]
+void acf_ext_host_channel(const AcfExtPlan& p, int c, int64_t cap, int64_t windows, int64_t ind_start,
+                          int64_t numOverLap, const uint8_t* cnt, const double* meanMax);
+// (acf_ext.cpp) the device path's: after acf_launch on ctx->stream with d.cnt set, the table's
+// upload, acf_spectrum_kernel, the download and the stores at [c * cap + m]; synchronises the stream
+int acf_ext_device(gnss_ctx* ctx, const AcfExtPlan& p, const AcfDev& d, int64_t cap);
 
 // Multi-device contexts (gnss_ctx_create_multi): the group's member contexts run their shards
 // side by side, one host thread per device (group.h has the dealing and merging).

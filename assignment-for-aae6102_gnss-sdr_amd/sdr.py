@@ -1250,7 +1250,7 @@ def _acf_records(records, prn, ctx, who):
 
 
 def acf_features(records, prnList, eleList, *, ctx: Context | None = None, want_index: bool = False,
-                 want_corr: bool = False, **params):
+                 want_corr: bool = False, extended: bool = False, **params):
     """The features of ACF/CalculateFeatures.m per channel (gnss_acf_features): a namespace of
     prn, ele, windows [n] and, per name of abi.ACF_FIELDS, a list of n arrays (one value per
     100-ms window): meanMax, F1 = meanMax / expectedCorr(ele), F2 = -meanDelay, varDelay,
@@ -1262,10 +1262,20 @@ def acf_features(records, prnList, eleList, *, ctx: Context | None = None, want_
     numOverLap, corrSpacing, maxDelay, a (abi.ACF_DEFAULTS). want_index / want_corr add
     maxCorrInd [n][max_len] (1-based arg-max per row) and corr [n][25][max_len], numpy arrays for
     host records and torch tensors on the device for device records. Host records need no GPU.
+
+    extended=True (gnss_acf_features_ext) adds, per name of abi.ACF_EXT_FIELDS, the features the
+    script keeps behind comment marks: numMLC (F6, the mean number of interior local maxima of a
+    row's 25 magnitudes), fftFreq and fftMag (F7 / F8, the largest line of an fft_n-point
+    spectrum of the channel's last fft_hist meanMax values: a reflected ray's fading frequency
+    and depth). Its params: fft_hist, fft_n, fft_fill (abi.ACF_EXT_DEFAULTS; fft_fill=1 takes only
+    the windows that exist in place of the script's zero-filled history), and fs, the windows per
+    second, by default 1000 / (numOverLap * pdi) with pdi = 1 (:172; 10 with the script's numbers).
     """
-    unknown = set(params) - set(abi.ACF_DEFAULTS)
+    ext_keys = set(abi.ACF_EXT_DEFAULTS) | {"fs", "pdi"}
+    unknown = set(params) - set(abi.ACF_DEFAULTS) - (ext_keys if extended else set())
     if unknown:
         raise TypeError(f"acf_features: unknown parameter(s) {sorted(unknown)}")
+    xpar = dict(abi.ACF_EXT_DEFAULTS, **{k: params.pop(k) for k in list(params) if k in ext_keys})
     par = dict(abi.ACF_DEFAULTS, **params)
     prn = [int(p) for p in np.atleast_1d(prnList)]
     ele = [float(e) for e in np.atleast_1d(eleList)]
@@ -1308,17 +1318,29 @@ def acf_features(records, prnList, eleList, *, ctx: Context | None = None, want_
             out.corr = corr.ctypes.data
     lib = abi.load()
     h = ctx.h if ctx is not None else None
-    st = lib.gnss_acf_features(h, C.byref(cfg), C.byref(rec), abi.MC_TAPS, C.byref(out))
+    if extended:
+        xcfg = abi.GnssAcfExtCfg()
+        xcfg.fft_hist, xcfg.fft_n, xcfg.fft_fill = int(xpar["fft_hist"]), int(xpar["fft_n"]), int(xpar["fft_fill"])
+        xcfg.fs = float(xpar["fs"]) if xpar.get("fs") is not None else 1000.0 / (nov * float(xpar.get("pdi", 1)))
+        xout = abi.GnssAcfExtOut()
+        for f in abi.ACF_EXT_FIELDS:
+            arr[f] = np.zeros((max(n, 1), cap))
+            setattr(xout, f, arr[f].ctypes.data_as(C.POINTER(C.c_double)))
+        st = lib.gnss_acf_features_ext(h, C.byref(cfg), C.byref(xcfg), C.byref(rec), abi.MC_TAPS, C.byref(out),
+                                       C.byref(xout))
+    else:
+        st = lib.gnss_acf_features(h, C.byref(cfg), C.byref(rec), abi.MC_TAPS, C.byref(out))
     if st != abi.OK:
         msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
         raise abi.GnssError(st, msg)
     res = SimpleNamespace(prn=prn, ele=ele, windows=windows[:n].copy(), maxCorrInd=ind, corr=corr)
-    for f in abi.ACF_FIELDS:
+    for f in arr:
         setattr(res, f, [arr[f][c, : windows[c]].copy() for c in range(n)])
     return res
 
 
-def CalculateFeatures(TckResults_multiCorr, prnList, eleList, *, ctx: Context | None = None, **params):
+def CalculateFeatures(TckResults_multiCorr, prnList, eleList, *, ctx: Context | None = None,
+                      extended: bool = False, **params):
     """ACF/CalculateFeatures.m:165-296 -> data_labeled, (1 + sum of the channels' windows) x 8:
     the script's all-zero first row (:165), then per PRN of prnList and per 100-ms window
     [prn, ele, meanMax, F1, F2, F3 = varDelay, F4 = meanCodeDisc, F5 = varCodeDisc] (:276-288).
@@ -1327,13 +1349,16 @@ def CalculateFeatures(TckResults_multiCorr, prnList, eleList, *, ctx: Context | 
     trackingCT_POS_updated_multicorrelator, trackingVT_POS_updated_multicorrelator) or their raw
     buffers, as for acf_features; prnList / eleList replace the script's hard-coded lists
     (:167-168) and params its hard-coded parameters (:172-179, :186). The plots of :298-323 are
-    not drawn."""
-    f = acf_features(TckResults_multiCorr, prnList, eleList, ctx=ctx, **params)
-    rows = [np.zeros((1, 8))]
+    not drawn. extended=True: the 11-column form the script's data sets once had (:32), with
+    F6 = numMLC, F7 = fftFreq, F8 = fftMag after F5 (acf_features' extended parameters)."""
+    f = acf_features(TckResults_multiCorr, prnList, eleList, ctx=ctx, extended=extended, **params)
+    fields = list(abi.ACF_FIELDS) + (list(abi.ACF_EXT_FIELDS) if extended else [])
+    ncol = 2 + len(fields)
+    rows = [np.zeros((1, ncol))]
     for c, (p, e) in enumerate(zip(f.prn, f.ele)):
         w = int(f.windows[c])
         rows.append(np.column_stack([np.full(w, float(p)), np.full(w, e)] +
-                                    [getattr(f, k)[c] for k in abi.ACF_FIELDS]).reshape(w, 8))
+                                    [getattr(f, k)[c] for k in fields]).reshape(w, ncol))
     return np.vstack(rows)
 
 

@@ -899,6 +899,71 @@ typedef struct gnss_acf_out {
 int gnss_acf_features(gnss_ctx *ctx, const gnss_acf_cfg *cfg, const gnss_track_out *records,
                       int32_t n_taps, gnss_acf_out *out);
 
+/* ---- CalculateFeatures.m's F6-F8 (additive within ABI v13; detected by symbol) -------------
+ * The three features the script keeps behind comment marks; its data sets were once 11 columns
+ * wide (:32). They look at how a channel's correlation changes from window to window: a
+ * reflected ray's carrier turns against the direct one's, so the prompt magnitude fades at the
+ * ray's Doppler difference. All arithmetic fp64, every operation rounded on its own (no
+ * contraction, no fast-math), every sum left to right from its first term (csrc/acf_ext.h is the
+ * one source for host and device). Windows, rows and corr(i, j) are gnss_acf_features': row m of
+ * channel c lines up with that call's rows, with gnss_acf_fit's and with the scene's labels.
+ *   - F6 numMLC(m): cnt(r) = the number of columns j = 2..24 (1-based) of row r with
+ *     corr(r, j) > corr(r, j-1) && corr(r, j) > corr(r, j+1) (:247-251). The edge columns never
+ *     count (the commented edge tests of :244-246 and :252-254 stay off), a plateau of equal
+ *     values counts nothing, a NaN compares false. numMLC(m) = (the exact integer sum of cnt over
+ *     the window's rows) / numOverLap, one division (:256).
+ *   - History: per channel a buffer of fft_hist values (:231, 300), all zero at the channel's
+ *     start (:293 resets it per PRN); at window m it is shifted left by one and meanMax(m) is
+ *     appended (:262). x[i], i = 0..H-1, is the buffer oldest first, H = fft_hist:
+ *     x[i] = meanMax(m - H + 1 + i), or 0 where that window lies before the channel's first. So a
+ *     record shorter than fft_hist windows (30 s with the defaults) mostly shows the step from
+ *     the zero fill. fft_fill = 1 is the one departure on offer: only the windows that exist
+ *     are taken, H = min(m + 1, fft_hist), no zero entries. Default 0, the script's form.
+ *   - Spectrum (:263-268): mean = (sum of x[i]) / H, y[i] = x[i] - mean; for k = 0..floor(N/2),
+ *     N = fft_n (:264, 1024), t = (k*i) mod N: re = sum_i y[i]*c[t], im = sum_i y[i]*s[t],
+ *     mag[k] = sqrt(re*re + im*im), with c[t] = cos((2*pi*t)/N) and s[t] = sin((2*pi*t)/N) from
+ *     one table that the host builds once per call with the C library (gnss_acf_twiddle returns
+ *     it); both paths read it, the device gets it uploaded. The script's fft has the other sign
+ *     of im, which mag does not see. The search stops at N/2: the upper bins of a real series
+ *     mirror the lower ones, and MATLAB's first-index max never picks them in exact arithmetic;
+ *     in rounded arithmetic a mirror bin could come out an ulp larger there, never here.
+ *   - I = the first index of the largest mag, 1-based, scanned as maxCorrInd is: from -1, taken
+ *     on v > best, a NaN as missing; if every bin is NaN (a NaN meanMax in the history), I = 1
+ *     and M = NaN. fftFreq = ((I-1)*fs)/N (:267), fftMag = M/(N/2) (:268): the script divides by
+ *     N/2 whatever H is, and so does this. */
+typedef struct gnss_acf_ext_cfg {
+    int32_t fft_hist;           /* :231, 2..512; default 300                                  */
+    int32_t fft_n;              /* :264, fft_hist..2048; default 1024                         */
+    int32_t fft_fill;           /* 0: zero-filled history (the script), 1: existing windows   */
+    int32_t reserved;
+    double  fs;                 /* :172, windows per second: 1000 / (numOverLap * pdi)        */
+} gnss_acf_ext_cfg;
+
+/* Caller-allocated host arrays, row-major [n][out->cap] each, as gnss_acf_out's six. */
+typedef struct gnss_acf_ext_out {
+    double *numMLC;           /* F6 (:256)                                                    */
+    double *fftFreq;          /* F7, Hz (:267)                                                */
+    double *fftMag;           /* F8 (:268)                                                    */
+} gnss_acf_ext_out;
+
+/* gnss_acf_features with F6-F8 beside it: everything that call does, `out` equal to that call's
+ * bit for bit (maxCorrInd and corr included), and ext filled as well. The same rules: host
+ * records need no GPU and ctx may be NULL; GNSS_OUT_DEVICE records run on the GPU (the row pass
+ * of csrc/acf.hip also writes cnt(r), one byte per row; csrc/acf_ext.hip, one block per window,
+ * forms the spectrum from the windows' meanMax in device memory); device records on a context of
+ * gnss_ctx_create_multi return GNSS_EARG. Both paths give the same bits in every output.
+ * GNSS_EARG also for everything gnss_acf_features refuses and for fft_hist outside 2..512, fft_n
+ * outside fft_hist..2048, fft_fill not 0 or 1, fs not finite or <= 0 and a null array: all
+ * checked on the host before any launch, the context usable after. gnss_acf_features itself is
+ * unchanged. */
+int gnss_acf_features_ext(gnss_ctx *ctx, const gnss_acf_cfg *cfg, const gnss_acf_ext_cfg *ext_cfg,
+                          const gnss_track_out *records, int32_t n_taps, gnss_acf_out *out,
+                          gnss_acf_ext_out *ext);
+
+/* The table both paths read: c[t] = cos((2*pi*t)/fft_n), s[t] = sin(...), t = 0..fft_n-1, from
+ * the C library. GNSS_EARG for fft_n outside 2..2048 or a null array. */
+int gnss_acf_twiddle(int32_t fft_n, double *c, double *s);
+
 /* ---- two-path fit of the 25-tap ACF (additive within ABI v13; detected by symbol) ---------
  * A multipath delay estimate per feature window: a direct path plus one reflected path fitted to
  * the coherently summed 25-tap correlation function. It goes beyond the reference, which has no
