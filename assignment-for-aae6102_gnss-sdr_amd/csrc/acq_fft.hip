@@ -322,10 +322,7 @@ __device__ __forceinline__ V tw_get(const TwIK<V>& tw, int i, int k, int m)
 }
 constexpr int kTwIK = 9 * 20 + 9 * 200;  // entries of the split layout
 // (every load of the block's prologue issued before the first LDS store: a loop of load ->
-// wait -> store paid one L2 round trip per iteration, 8 per table, GNSS_STAGED_LOADS 0)
-#ifndef GNSS_STAGED_LOADS
-#define GNSS_STAGED_LOADS 1
-#endif
+// wait -> store paid one L2 round trip per iteration, 8 per table, profiles/r05_ab_staged_loads.txt)
 template <class V>
 __device__ __forceinline__ TwIK<V> load_row_tw_ik(V* s_t, const V* tw_row, int tid)
 {
@@ -335,20 +332,16 @@ __device__ __forceinline__ TwIK<V> load_row_tw_ik(V* s_t, const V* tw_row, int t
         const int i = t2 ? f / 20 + 1 : f / 200 + 1, k = t2 ? f % 20 : f % 200;
         return t2 ? 10 * i * k : i * k;
     };
-    if constexpr (GNSS_STAGED_LOADS) {
-        constexpr int NIT = (kTwIK + kRowThreads - 1) / kRowThreads;
-        V r[NIT];
+    constexpr int NIT = (kTwIK + kRowThreads - 1) / kRowThreads;
+    V r[NIT];
 #pragma unroll
-        for (int q = 0; q < NIT; q++) {
-            const int e0 = tid + q * kRowThreads;
-            r[q] = tw_row[src(e0 < kTwIK ? e0 : kTwIK - 1)];
-        }
-#pragma unroll
-        for (int q = 0; q < NIT; q++)
-            if (tid + q * kRowThreads < kTwIK) s_t[tid + q * kRowThreads] = r[q];
-    } else {
-        for (int e = tid; e < kTwIK; e += kRowThreads) s_t[e] = tw_row[src(e)];
+    for (int q = 0; q < NIT; q++) {
+        const int e0 = tid + q * kRowThreads;
+        r[q] = tw_row[src(e0 < kTwIK ? e0 : kTwIK - 1)];
     }
+#pragma unroll
+    for (int q = 0; q < NIT; q++)
+        if (tid + q * kRowThreads < kTwIK) s_t[tid + q * kRowThreads] = r[q];
     return TwIK<V>{s_t, s_t + 9 * 20};
 }
 
@@ -523,19 +516,15 @@ __global__ __launch_bounds__(kRowThreads) void fwd_rows_kernel(
             const R xr = (R)r.x, xi = (R)r.y;
             s_a[n1] = mk<V>(fma2(xr, c, -(xi * sn)), fma2(xr, sn, xi * c));
         };
-        if constexpr (GNSS_STAGED_LOADS) {
-            double2 raw[NIT];
+        double2 raw[NIT];
 #pragma unroll
-            for (int q = 0; q < NIT; q++) {
-                const int m0 = tid + q * kRowThreads, n1 = m0 < kRow ? m0 : kRow - 1;
-                raw[q] = src.at((int64_t)idx * S + (int64_t)P * n1 + n2);
-            }
-#pragma unroll
-            for (int q = 0; q < NIT; q++)
-                if (tid + q * kRowThreads < kRow) put(tid + q * kRowThreads, raw[q]);
-        } else {
-            for (int n1 = tid; n1 < kRow; n1 += kRowThreads) put(n1, src.at((int64_t)idx * S + (int64_t)P * n1 + n2));
+        for (int q = 0; q < NIT; q++) {
+            const int m0 = tid + q * kRowThreads, n1 = m0 < kRow ? m0 : kRow - 1;
+            raw[q] = src.at((int64_t)idx * S + (int64_t)P * n1 + n2);
         }
+#pragma unroll
+        for (int q = 0; q < NIT; q++)
+            if (tid + q * kRowThreads < kRow) put(tid + q * kRowThreads, raw[q]);
     } else {
         const float* cp = ca + (int64_t)(s - nsig) * 1023;
         auto chip = [&](int n1) {
@@ -543,19 +532,15 @@ __global__ __launch_bounds__(kRowThreads) void fwd_rows_kernel(
             const int64_t ci = (int64_t)ceil((double)(n + 1) * code_step);  // 1-based into [CA CA]
             return (ci - 1) % 1023;
         };
-        if constexpr (GNSS_STAGED_LOADS) {
-            float cv[NIT];
+        float cv[NIT];
 #pragma unroll
-            for (int q = 0; q < NIT; q++) {
-                const int m0 = tid + q * kRowThreads;
-                cv[q] = cp[chip(m0 < kRow ? m0 : kRow - 1)];
-            }
-#pragma unroll
-            for (int q = 0; q < NIT; q++)
-                if (tid + q * kRowThreads < kRow) s_a[tid + q * kRowThreads] = mk<V>((R)cv[q], (R)0);
-        } else {
-            for (int n1 = tid; n1 < kRow; n1 += kRowThreads) s_a[n1] = mk<V>((R)cp[chip(n1)], (R)0);
+        for (int q = 0; q < NIT; q++) {
+            const int m0 = tid + q * kRowThreads;
+            cv[q] = cp[chip(m0 < kRow ? m0 : kRow - 1)];
         }
+#pragma unroll
+        for (int q = 0; q < NIT; q++)
+            if (tid + q * kRowThreads < kRow) s_a[tid + q * kRowThreads] = mk<V>((R)cv[q], (R)0);
     }
     __syncthreads();
     V* o = B + ((int64_t)s * P + n2) * kRow;
@@ -593,18 +578,7 @@ template <> __device__ __forceinline__ float2 buf_ld<float2>(__amdgpu_buffer_rsr
     const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
     return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
 }
-#ifndef GNSS_COLS_BUF
-#define GNSS_COLS_BUF 1  // (A/B: 0 = the column pass's plain loads)
-#endif
-#ifndef GNSS_COLS_GROUP
-#define GNSS_COLS_GROUP 8  // (A/B: signal-spectrum rows per load group of the column pass)
-#endif
-#ifndef GNSS_TW_ROWS
-#define GNSS_TW_ROWS 1  // (A/B: 0 = the column pass multiplies by the four-step twiddle)
-#endif
-#ifndef GNSS_INVCOLS_WPE
-#define GNSS_INVCOLS_WPE 0  // (A/B: waves per EU asked of inv_cols; 0 = the compiler's choice)
-#endif
+constexpr int kColsGroup = 8;  // signal-spectrum rows per load group of the column pass
 // (the body takes its block coordinates: inv_cols_kernel and the paired launch run it)
 template <int P, class V>
 __device__ __forceinline__ void inv_cols_body(
@@ -616,92 +590,48 @@ __device__ __forceinline__ void inv_cols_body(
     const int q = first_pair + t / datalen, idx = t % datalen;
     const int bin = q / nprn, p = q - bin * nprn;
     V v[P];
-    if (GNSS_COLS_BUF == 2) {
-        // (A/B) code and signal rows loaded together, G rows at a time with the next G in
-        // flight: fewer registers held than all code rows first
-        constexpr int kB = P * kRow * (int)sizeof(V), G = GNSS_COLS_GROUP;
-        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(C + (int64_t)p * P * kRow), (short)0, kB, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(X + ((int64_t)idx * nbins + bin) * P * kRow), (short)0, kB, 0x00020000);
-        const int vo = k1 * (int)sizeof(V);
-        V ca[G], xa[G];
+    // buffer loads (row offsets in SGPRs: no per-load 64-bit address arithmetic), every
+    // code-spectrum value first, then the signal spectrum 8 rows at a time with the next 8
+    // in flight: the lane waits for L2 about 4 times, not once per row as the compiler's
+    // interleaved schedule did (profiles/r04_ab_acq_cols.txt)
+    constexpr int kB = P * kRow * (int)sizeof(V), G = kColsGroup;
+    const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(C + (int64_t)p * P * kRow), (short)0, kB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(X + ((int64_t)idx * nbins + bin) * P * kRow), (short)0, kB, 0x00020000);
+    const int vo = k1 * (int)sizeof(V);
 #pragma unroll
-        for (int i = 0; i < G; i++) {
-            const int r = (i < P ? i : P - 1) * kRow * (int)sizeof(V);
-            ca[i] = buf_ld<V>(rc, vo, r);
-            xa[i] = buf_ld<V>(rx, vo, r);
-        }
+    for (int i = 0; i < P; i++) v[i] = buf_ld<V>(rc, vo, i * kRow * (int)sizeof(V));
+    V xa[G];
 #pragma unroll
-        for (int g = 0; g < P; g += G) {
-            V cb[G], xb[G];
+    for (int i = 0; i < G; i++) xa[i] = buf_ld<V>(rx, vo, (i < P ? i : P - 1) * kRow * (int)sizeof(V));
 #pragma unroll
-            for (int i = 0; i < G; i++)
-                if (g + G + i < P) {
-                    cb[i] = buf_ld<V>(rc, vo, (g + G + i) * kRow * (int)sizeof(V));
-                    xb[i] = buf_ld<V>(rx, vo, (g + G + i) * kRow * (int)sizeof(V));
-                }
-            __builtin_amdgcn_sched_barrier(0);
+    for (int g = 0; g < P; g += G) {
+        V xb[G];
 #pragma unroll
-            for (int i = 0; i < G; i++)
-                if (g + i < P) v[g + i] = cmulc(ca[i], xa[i]);
+        for (int i = 0; i < G; i++)
+            if (g + G + i < P) xb[i] = buf_ld<V>(rx, vo, (g + G + i) * kRow * (int)sizeof(V));
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < G; i++) { ca[i] = cb[i]; xa[i] = xb[i]; }
-        }
-    } else if (GNSS_COLS_BUF) {
-        // buffer loads (row offsets in SGPRs: no per-load 64-bit address arithmetic), every
-        // code-spectrum value first, then the signal spectrum 8 rows at a time with the next 8
-        // in flight: the lane waits for L2 about 4 times, not once per row as the compiler's
-        // interleaved schedule did
-        constexpr int kB = P * kRow * (int)sizeof(V), G = GNSS_COLS_GROUP;
-        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(C + (int64_t)p * P * kRow), (short)0, kB, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(X + ((int64_t)idx * nbins + bin) * P * kRow), (short)0, kB, 0x00020000);
-        const int vo = k1 * (int)sizeof(V);
+        for (int i = 0; i < G; i++)
+            if (g + i < P) v[g + i] = cmulc(v[g + i], xa[i]);
 #pragma unroll
-        for (int i = 0; i < P; i++) v[i] = buf_ld<V>(rc, vo, i * kRow * (int)sizeof(V));
-        V xa[G];
-#pragma unroll
-        for (int i = 0; i < G; i++) xa[i] = buf_ld<V>(rx, vo, (i < P ? i : P - 1) * kRow * (int)sizeof(V));
-#pragma unroll
-        for (int g = 0; g < P; g += G) {
-            V xb[G];
-#pragma unroll
-            for (int i = 0; i < G; i++)
-                if (g + G + i < P) xb[i] = buf_ld<V>(rx, vo, (g + G + i) * kRow * (int)sizeof(V));
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < G; i++)
-                if (g + i < P) v[g + i] = cmulc(v[g + i], xa[i]);
-#pragma unroll
-            for (int i = 0; i < G; i++) xa[i] = xb[i];
-        }
-    } else {
-        const V* c = C + (int64_t)p * P * kRow + k1;
-        const V* x = X + ((int64_t)idx * nbins + bin) * P * kRow + k1;
-#pragma unroll
-        for (int i = 0; i < P; i++) v[i] = cmulc(c[(int64_t)i * kRow], x[(int64_t)i * kRow]);
+        for (int i = 0; i < G; i++) xa[i] = xb[i];
     }
     V* a = A + (int64_t)t * P * kRow + k1;
-    const V* tw = tw_col + k1;
     // A is streamed once (to the row pass): non-temporal stores keep C and X in the caches.
-    // GNSS_TW_ROWS: the four-step twiddle w^(k1 k2) is applied by the row pass as it loads
-    // the row (the same product of the same operands: same bits), so this pass issues no
-    // load after its first store -- on gfx9 a load's vmcnt wait also waits for every store
-    // issued before it, and the twiddle reads between the stores serialised them.
+    // The four-step twiddle w^(k1 k2) is applied by the row pass as it loads the row (the
+    // same product of the same operands: same bits; tw_col is not read here), so this pass
+    // issues no load after its first store -- on gfx9 a load's vmcnt wait also waits for every
+    // store issued before it, and the twiddle reads between the stores serialised them.
     dft_prime<P, 1>(v, [&](int k, V y) {
-        const V z = GNSS_TW_ROWS ? y : cmulc(y, tw[(int64_t)k * kRow]);
-        __builtin_nontemporal_store(z.x, &a[(int64_t)k * kRow].x);
-        __builtin_nontemporal_store(z.y, &a[(int64_t)k * kRow].y);
+        __builtin_nontemporal_store(y.x, &a[(int64_t)k * kRow].x);
+        __builtin_nontemporal_store(y.y, &a[(int64_t)k * kRow].y);
     });
 }
 
 template <int P, class V>
 __global__ __launch_bounds__(kColThreads)
-#if GNSS_INVCOLS_WPE > 0
-__attribute__((amdgpu_waves_per_eu(GNSS_INVCOLS_WPE, GNSS_INVCOLS_WPE)))
-#endif
 void inv_cols_kernel(
     const V* __restrict__ C, const V* __restrict__ X, int nbins, int nprn, int datalen,
     int first_pair, const V* __restrict__ tw_col, V* __restrict__ A)
@@ -743,7 +673,7 @@ __global__ __launch_bounds__(kRowThreads) void inv_rows_kernel(
         v.w = __builtin_nontemporal_load(&q->w);
         return v;
     };
-    // (GNSS_TW_ROWS) this row's four-step twiddles w^(tau2 k1), k1 = 2e, 2e + 1, held for every ms
+    // this row's four-step twiddles w^(tau2 k1), k1 = 2e, 2e + 1, held for every ms
     float4 tw4[QV];
 #pragma unroll
     for (int i = 0; i < QV; i++) {
@@ -752,11 +682,9 @@ __global__ __launch_bounds__(kRowThreads) void inv_rows_kernel(
     }
     auto st = [&](int h, int i, float4 v) {
         const int e = tid + i * kRowThreads;
-        if (GNSS_TW_ROWS) {
-            const float2 lo = cmulc(make_float2(v.x, v.y), make_float2(tw4[i].x, tw4[i].y));
-            const float2 hi = cmulc(make_float2(v.z, v.w), make_float2(tw4[i].z, tw4[i].w));
-            v = make_float4(lo.x, lo.y, hi.x, hi.y);
-        }
+        const float2 lo = cmulc(make_float2(v.x, v.y), make_float2(tw4[i].x, tw4[i].y));
+        const float2 hi = cmulc(make_float2(v.z, v.w), make_float2(tw4[i].z, tw4[i].w));
+        v = make_float4(lo.x, lo.y, hi.x, hi.y);
         if (e < V4) s_a4[h * V4 + e] = v;
     };
     float4 a0 = ld(0, 0), a1 = ld(0, 1), a2 = ld(0, 2), a3 = ld(0, 3);
@@ -823,20 +751,18 @@ __device__ __forceinline__ void inv_rows_f64_body(
         n3 = ld_nt(r + 3 * kRowThreads); n4 = ld_nt(r + 4 * kRowThreads);                      \
         n5 = ld_nt(r + 5 * kRowThreads); n6 = ld_nt(r + 6 * kRowThreads); n7 = ld_nt(r + e7 - tid); \
     }
-    // (GNSS_TW_ROWS) this row's four-step twiddles w^(tau2 k1) for the lane's 8 elements, held
+    // this row's four-step twiddles w^(tau2 k1) for the lane's 8 elements, held
     // for every ms: the column pass's product cmulc(y, w), moved here
     double2 w0, w1, w2, w3, w4, w5, w6, w7;
-    if (GNSS_TW_ROWS) {
+    {
         const double2* t = tw_col + (int64_t)tau2 * kRow + tid;
         w0 = t[0]; w1 = t[kRowThreads]; w2 = t[2 * kRowThreads]; w3 = t[3 * kRowThreads];
         w4 = t[4 * kRowThreads]; w5 = t[5 * kRowThreads]; w6 = t[6 * kRowThreads]; w7 = t[e7 - tid];
     }
     GNSS_LD(0)
     for (int idx = 0; idx < datalen; idx++) {
-        if (GNSS_TW_ROWS) {
-            n0 = cmulc(n0, w0); n1 = cmulc(n1, w1); n2 = cmulc(n2, w2); n3 = cmulc(n3, w3);
-            n4 = cmulc(n4, w4); n5 = cmulc(n5, w5); n6 = cmulc(n6, w6); n7 = cmulc(n7, w7);
-        }
+        n0 = cmulc(n0, w0); n1 = cmulc(n1, w1); n2 = cmulc(n2, w2); n3 = cmulc(n3, w3);
+        n4 = cmulc(n4, w4); n5 = cmulc(n5, w5); n6 = cmulc(n6, w6); n7 = cmulc(n7, w7);
         s_a[tid] = n0; s_a[tid + kRowThreads] = n1; s_a[tid + 2 * kRowThreads] = n2;
         s_a[tid + 3 * kRowThreads] = n3; s_a[tid + 4 * kRowThreads] = n4;
         s_a[tid + 5 * kRowThreads] = n5; s_a[tid + 6 * kRowThreads] = n6;
@@ -1003,10 +929,7 @@ __global__ __launch_bounds__(kRowThreads, 2) void inv_fused_kernel_f64(
 #pragma unroll
                 for (int i = 0; i < P; i++) v[i] = cmulc(c[(int64_t)i * kRow], ld_nt(x + (int64_t)i * kRow));
                 double2* a = ring_x + (int64_t)slot * S + k1;
-                const double2* tw = tw_col + k1;
-                dft_prime<P, 1>(v, [&](int k, double2 y) {
-                    a[(int64_t)k * kRow] = GNSS_TW_ROWS ? y : cmulc(y, tw[(int64_t)k * kRow]);
-                });
+                dft_prime<P, 1>(v, [&](int k, double2 y) { a[(int64_t)k * kRow] = y; });
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's stores are in L2
             __syncthreads();
@@ -1035,7 +958,7 @@ __global__ __launch_bounds__(kRowThreads, 2) void inv_fused_kernel_f64(
                 typedef unsigned u4 __attribute__((ext_vector_type(4)));
                 const u4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, row0 + e * 16, 0, 16 /* sc1 */);
                 const double2 y = make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
-                s_a[e] = GNSS_TW_ROWS ? cmulc(y, tw_col[(int64_t)tau2 * kRow + e]) : y;
+                s_a[e] = cmulc(y, tw_col[(int64_t)tau2 * kRow + e]);  // (the four-step twiddle, as in the row pass)
             }
         }
         __syncthreads();  // the row is in LDS: the slot may be refilled
@@ -1099,17 +1022,11 @@ __device__ __forceinline__ int64_t fine_code_of(int64_t n, double invFs, double 
 
 // A row of the fine search reads the samples n = P*T*m1 + rho, m1 < 2000: a lane stride of
 // P*T samples, one cache line per lane for 2 bytes of it, and each of the D row passes of a
-// column rho reads them again. GNSS_FINE_PREP: one pass per SV first copies CarrSignal's
+// column rho reads them again. One pass per SV first copies CarrSignal's
 // samples (unconverted) and their chips (the CA table's float at the chip index) into the
 // row order [rho][m1] through an LDS tile (TM consecutive m1 x every rho: a contiguous run of
 // the record), so the row pass reads both contiguously and with no dependent table read;
 // the values are the ones it computed itself.
-#ifndef GNSS_FINE_PREP
-#define GNSS_FINE_PREP 1
-#endif
-#ifndef GNSS_FINE_TWIK
-#define GNSS_FINE_TWIK 1
-#endif
 template <class Src> struct SrcElem;
 template <> struct SrcElem<SrcIQ8> {
     using T = char2;
@@ -1152,7 +1069,8 @@ __global__ __launch_bounds__(kRowThreads) void fine_prep_kernel(
 }
 
 // (blockIdx.z = the SV of a batched launch: its code delay, code table and transform slab)
-// GNSS_FINE_PREP: `src` is the prep pass's [sv][rho][m1] copy and ct its chips.
+// `src` is the prep pass's [sv][rho][m1] copy and ct its chips (cd .. codelength and tw_row
+// describe the record the prep pass read: this kernel no longer needs them).
 template <int P, class Src>
 __global__ __launch_bounds__(kRowThreads) void fine_rows_kernel(
     const Src src, const float* __restrict__ ct, const int32_t* __restrict__ cd, int64_t S,
@@ -1161,17 +1079,13 @@ __global__ __launch_bounds__(kRowThreads) void fine_rows_kernel(
     const double2* __restrict__ tabB, double2* __restrict__ E0)
 {
     constexpr int T = kFineT;
-    const int64_t base = S - cd[blockIdx.z] - 1;  // 0-based sample of CarrSignal(1) (acquisition.m:105)
-    const float* ca = ca0 + (int64_t)blockIdx.z * 1023;
     double2* E = E0 + (int64_t)blockIdx.z * N;
     // twiddles read from the (L2-resident) global table: 32 KB of LDS per block instead of
     // 64, five blocks per CU instead of two
     __shared__ double2 s_a[kRowPad];
     const int rho = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
     const int m2 = rho / P, n2 = rho - m2 * P;
-    auto sample = [&](int m1) { return (int64_t)P * T * m1 + (int64_t)P * m2 + n2; };
-    auto code_of = [&](int64_t n) { return fine_code_of(n, invFs, invFc, codelength); };
-    if constexpr (GNSS_FINE_PREP) {
+    {
         constexpr int NIT = (kRow + kRowThreads - 1) / kRowThreads;
         const int64_t row0 = ((int64_t)blockIdx.z * P * T + rho) * kRow;
         double2 raw[NIT], ta[NIT];
@@ -1190,33 +1104,6 @@ __global__ __launch_bounds__(kRowThreads) void fine_rows_kernel(
             const double2 x = make_double2(raw[q].x * code, raw[q].y * code);
             if (m1 < kRow) s_a[m1] = cmul(x, ta[q]);
         }
-    } else if constexpr (GNSS_STAGED_LOADS) {
-        constexpr int NIT = (kRow + kRowThreads - 1) / kRowThreads;
-        double2 raw[NIT], ta[NIT];
-        float cv[NIT];
-#pragma unroll
-        for (int q = 0; q < NIT; q++) {
-            const int m10 = tid + q * kRowThreads, m1 = m10 < kRow ? m10 : kRow - 1;
-            const int64_t n = sample(m1);
-            cv[q] = ca[code_of(n)];
-            raw[q] = src.at(base + n);
-            ta[q] = tabA[(int64_t)r * kRow + m1];
-        }
-#pragma unroll
-        for (int q = 0; q < NIT; q++) {
-            const int m1 = tid + q * kRowThreads;
-            const double code = (double)cv[q];
-            const double2 x = make_double2(raw[q].x * code, raw[q].y * code);
-            if (m1 < kRow) s_a[m1] = cmul(x, ta[q]);  // w_RD^(-m1*r), [r][m1]: coalesced
-        }
-    } else {
-        for (int m1 = tid; m1 < kRow; m1 += kRowThreads) {
-            const int64_t n = sample(m1);
-            const double code = (double)ca[code_of(n)];
-            const double2 raw = src.at(base + n);
-            const double2 x = make_double2(raw.x * code, raw.y * code);
-            s_a[m1] = cmul(x, tabA[(int64_t)r * kRow + m1]);  // w_RD^(-m1*r), [r][m1]: coalesced
-        }
     }
     __syncthreads();
     double sn, cs;
@@ -1226,13 +1113,10 @@ __global__ __launch_bounds__(kRowThreads) void fine_rows_kernel(
     double2* o = E + (((int64_t)r * P + n2) * T + m2) * kRow;
     const double2* tb = tabB + m2 * kRow;  // w_{T*2000}^(-m2*j1), [m2][j1]
     auto put = [&](int, int j1, double2 v) { o[j1] = cmul(cmul(v, cb), tb[j1]); };
-    // GNSS_FINE_TWIK: the stages' twiddles from the global split table (coalesced: lanes read
+    // the stages' twiddles from the global split table (coalesced: lanes read
     // consecutive entries) instead of the plain table (a gather at a lane stride of i or 10 i
     // entries: up to a cache line per lane); the same values
-    if constexpr (GNSS_FINE_TWIK)
-        fft2000_r20first_put<-1>(s_a, TwIK<double2>{twik, twik + 9 * 20}, tid, put);
-    else
-        fft2000_r20first_put<-1>(s_a, tw_row, tid, put);
+    fft2000_r20first_put<-1>(s_a, TwIK<double2>{twik, twik + 9 * 20}, tid, put);
 }
 
 struct FineBest {
@@ -1264,7 +1148,7 @@ __global__ __launch_bounds__(kColThreads) void fine_cols_kernel(
         const int jj = e % JC, nm = e / JC;  // nm = n2*T + m2
         return E + ((int64_t)r * P * T + nm) * kRow + j10 + jj;
     };
-    if constexpr (GNSS_STAGED_LOADS) {
+    {
         constexpr int NE = P * T * JC, NIT = (NE + kColThreads - 1) / kColThreads;
         double2 st[NIT];
 #pragma unroll
@@ -1275,8 +1159,6 @@ __global__ __launch_bounds__(kColThreads) void fine_cols_kernel(
 #pragma unroll
         for (int q = 0; q < NIT; q++)
             if (tid + q * kColThreads < NE) s_e[tid + q * kColThreads] = st[q];
-    } else {
-        for (int e = tid; e < P * T * JC; e += kColThreads) s_e[e] = *at(e);
     }
     __syncthreads();
     // DFT_T over m2 for each (n2, jj), twiddle w_M^(-n2*k1), k1 = k + 2000*j2:
@@ -1525,7 +1407,7 @@ FineLayout fine_layout(int64_t S, int L, int datalen)
 }
 }  // namespace
 
-// (GNSS_FINE_PREP) the row-order copies after the candidates: nsv x M samples (sized for the
+// the row-order copies after the candidates: nsv x M samples (sized for the
 // widest source, complex fp64), then nsv x M chips (float)
 static size_t fine_prep_offset(const FineLayout& f, int nsv)
 {
@@ -1535,7 +1417,6 @@ static size_t fine_prep_offset(const FineLayout& f, int nsv)
 size_t fine_fft_scratch_bytes(int64_t S, int L, int datalen, int nsv)
 {
     const FineLayout f = fine_layout(S, L, datalen);
-    if (!GNSS_FINE_PREP) return fine_prep_offset(f, nsv);
     return fine_prep_offset(f, nsv) + (size_t)nsv * f.M * (sizeof(double2) + sizeof(float));
 }
 
@@ -1584,14 +1465,12 @@ hipError_t launch_fine_fft_argmax(const int8_t* iq, const double2* xs, int64_t S
     char* prep = static_cast<char*>(scratch) + fine_prep_offset(f, nsv);
     float* ct = reinterpret_cast<float*>(prep + (size_t)nsv * f.M * sizeof(double2));
     const int nblk = kRow / kFineJC;
-    // the row pass over source Src: from the record itself, or (GNSS_FINE_PREP) from its row-order copy
+    // the row pass over source Src: from the row-order copy of the record (fine_prep_kernel)
     auto rows = [&](auto src, auto* xt, auto kern, auto prep_kern, int tm) {
         using SrcT = decltype(src);
-        if (GNSS_FINE_PREP) {
-            hipLaunchKernelGGL(prep_kern, dim3((kRow + tm - 1) / tm, nsv), dim3(kRowThreads), 0, s, src, cd, S, 1 / Fs,
-                               1 / codeFreqBasis, codelength, ca, xt, ct);
-            src = SrcElem<SrcT>::wrap(xt);
-        }
+        hipLaunchKernelGGL(prep_kern, dim3((kRow + tm - 1) / tm, nsv), dim3(kRowThreads), 0, s, src, cd, S, 1 / Fs,
+                           1 / codeFreqBasis, codelength, ca, xt, ct);
+        src = SrcElem<SrcT>::wrap(xt);
         hipLaunchKernelGGL(kern, dim3((unsigned)(f.M / kRow), datalen, nsv), dim3(kRowThreads), 0, s, src, ct, cd, S,
                            ca, 1 / Fs, 1 / codeFreqBasis, codelength, datalen, N, tw_row, tabS + f.M / kRow, tabA,
                            tabB, E);

@@ -14,11 +14,6 @@ namespace {
 // (GNSS_OPT_ACQ_PIPE; config-2 fp64 correlation 10.10-10.18 -> 9.75-9.88 ms on MI355X,
 // profiles/r03_ab_acq_pipe.txt).
 constexpr int kAcqPipeDefault = 2;
-// the pipeline's forward spectra in bin chunks, each before the first column pass that reads it
-#ifndef GNSS_ACQ_FWD_SPLIT
-#define GNSS_ACQ_FWD_SPLIT 1
-#endif
-constexpr bool kAcqFwdSplit = GNSS_ACQ_FWD_SPLIT;
 // the paired launch's row blocks sit in the grid's first kAcqPairFront percent (acq_fft.hip)
 constexpr int kAcqPairFront = 60;
 // SVs per launch of the fine-frequency search (scratch ~186 MB per SV at config 2)
@@ -121,12 +116,12 @@ int acq_search(gnss_ctx* ctx, const int8_t* blk, const double2* xa, int64_t S, i
         HIP_TRY(A.alloc(ctx, "acq.A", csz * abuf * (two || pair ? 2 : 1)));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         HIP_TRY(hipEventRecord(e_all.a, ctx->stream));
-        // the forward spectra: all at once, or (the two-stream pipeline, GNSS_ACQ_FWD_SPLIT) the
+        // the forward spectra: all at once, or (the two-stream pipeline) the
         // codes and the bins batch 0 reads first and each later batch's new bins just before its
         // column pass, on the column stream, where they run beside the previous batch's row pass
         // (the column stream waits on the rows anyway); every spectrum is the same transform of the
-        // same data, so the bits do not change
-        const bool fwd_split = kAcqFwdSplit && two;
+        // same data, so the bits do not change (profiles/r05_ab_fwd_split.txt)
+        const bool fwd_split = two;
         auto fwd = [&](int bin0, int nbc, bool codes) {
             return launch_acq_fft_forward<V>(blk, xa, S, dl, nb, sg->IF, acq->freqMin, acq->freqStep, sg->Fs, ca, np,
                                              sg->codeFreqBasis, d_twr.as<V>(), d_twc.as<V>(), B.as<V>(), X.as<V>(),
@@ -143,8 +138,6 @@ int acq_search(gnss_ctx* ctx, const int8_t* blk, const double2* xa, int64_t S, i
         }
         const V* C = X.as<V>() + (size_t)nsig * S;
         if (pair) {
-            const char* fe = probe_env("GNSS_PAIR_FRONT");  // (probe builds: the A/B knob)
-            const int front = fe ? atoi(fe) : kAcqPairFront;
             const int nbt = (npairs + batch - 1) / batch;
             double2* Ah[2] = {reinterpret_cast<double2*>(A.p), reinterpret_cast<double2*>(A.p) + abuf};
             for (int b = 0; b <= nbt; b++) {
@@ -153,7 +146,7 @@ int acq_search(gnss_ctx* ctx, const int8_t* blk, const double2* xa, int64_t S, i
                 const int nr = b > 0 ? std::min(batch, npairs - rq) : 0;
                 HIP_TRY(launch_acq_fft_pair(reinterpret_cast<const double2*>(C), X.as<double2>(), S, dl, nb, np, cq,
                                             nc, Ah[b & 1], rq, nr, Ah[(b + 1) & 1], d_twr.as<double2>(),
-                                            d_twc.as<double2>(), reinterpret_cast<double*>(corr), front,
+                                            d_twc.as<double2>(), reinterpret_cast<double*>(corr), kAcqPairFront,
                                             ctx->stream));
             }
             return GNSS_OK;

@@ -554,20 +554,13 @@ static int tracking_impl(gnss_ctx* ctx, const gnss_file* file, const gnss_signal
     // resident (config 5: 32 channels x 11 taps), each block correlates vpb of the step's
     // blocks in turn -- the lane geometry and so the bits stay those of bpc blocks.
     // GNSS_OPT_FORCE_VPB (test hook) asks for at least that many.
-    // above 3 taps the persistent loop's lanes keep at most kQcapMax interior tap boundaries
-    // (lane_correlate's capture queue): checked here for code rates up to cps_max, and a step
-    // beyond that rate stops the channel with GNSS_EINDEX in the kernel (as d*M >= 1 does)
-    P.qcap_dmax = cps_max;
+    P.cps_max = cps_max;
     // <= 3 taps: tap prefixes from the capture register wherever a lane holds at most
     // kRegCapMax distinct boundary samples (lane_boundaries), else through the LDS slots
     P.regcap = regcap_mask(P, cps_max, ctx->opt[GNSS_OPT_SLOT_PATH]);
-    auto qcap_ok = [&](int sub) {
-        return !GNSS_QCAP || P.ntaps <= 3 ||
-               max_taps_in_lane(P.taps, P.tap_post, P.ntaps, 8 * sub, cps_max) <= kQcapMax;
-    };
     auto vpb_for = [&](int bpc, int sub) {
         const bool no_persist = ctx->opt[GNSS_OPT_NO_PERSIST] || P.fmt != 0 || wide_taps ||
-                                bpc > run_bpc_cap(P.ntaps) || !qcap_ok(sub);
+                                bpc > run_bpc_cap(P.ntaps);
         return geom::vpb_for(no_persist, nch, bpc, cus, ctx->opt[GNSS_OPT_FORCE_VPB],
                              [&] { return track_run_blocks_per_cu(P, sub, false); },
                              [&] { return track_run_blocks_per_cu(P, sub, true); });

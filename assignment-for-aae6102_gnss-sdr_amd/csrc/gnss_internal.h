@@ -159,7 +159,7 @@ GNSS_HD double div_markstein(double x, double b, double rb)
 
 // sin and cos of a small argument (|x| <= ~40 rad: the lane's reduced carrier phase, the rotation
 // table's phi[m], a VT sample's 2*pi-reduced phase) with a short dependent chain, for the
-// correlators' lane rotation and the rotation table (track.hip GNSS_FAST_SINCOS; 0 = the device
+// correlators' lane rotation and the rotation table (track.hip, in place of the device
 // library's sincos) and the VT step's samples (vt.hip). Reduction by pi/2 in two
 // parts (q * PIO2_HI exact for |q| < 2^20: PIO2_HI has 33 significant bits), then the classic
 // fdlibm minimax kernels on [-pi/4, pi/4] (__kernel_sin / __kernel_cos, error < 1 ulp), the two
@@ -283,10 +283,11 @@ struct TrkParams {
     const long long* pref_q;  //   (8-sample groups from buf_base), Q likewise
     const short* stage16;     // fmt 1: the staged int16 I/Q (absolute: stage16[2k] = I of k)
     double taps[GNSS_MAX_TAPS];
-    // the persistent loop above 3 taps (lane_correlate's capture queue, at most kQcapMax
-    // interior boundaries per lane): the host checked that bound for code rates up to this many
-    // chips per sample; a step beyond it stops the channel with GNSS_EINDEX, as d*M >= 1 does
-    double qcap_dmax;
+    // the largest code rate (chips per sample) the host planned the lanes for. No kernel
+    // decides anything from it; the persistent loop still carries it among its scalar constants
+    // (TailK), because taking it out moves that loop's register allocation: 21 of its forms
+    // then spill differently and most grow by 1-119 instructions (profiles/knob_removal.txt)
+    double cps_max;
     // Loop conventions: 0 = trackingCT.m; 1 = trackingCT_POS_updated.m:179-408 (numSample
     // by ceil, prompt replica Code(ceil(t + 0.05) + 1), codeFreq = f0 + codeNco, loop T =
     // signal.ms for every pdi, Index + 1 per step, no phase-C negation or re-seek,
@@ -390,14 +391,6 @@ hipError_t launch_track_expand(const double* src, int64_t rec_cap, int stride, i
 #define GNSS_PROBE_BUILD 0
 #endif
 constexpr bool kProbe = GNSS_PROBE_BUILD != 0;
-// A/B knobs of the tracking exchange (tools/build_variant.sh; product: 0): s_sleep between
-// the sweep's poll rounds, and a channel's blocks on one XCD (8 channels).
-#ifndef GNSS_XCHG_SLEEP
-#define GNSS_XCHG_SLEEP 0
-#endif
-#ifndef GNSS_XCD_LOCAL
-#define GNSS_XCD_LOCAL 0
-#endif
 
 constexpr int kTrkThreads = 256;
 constexpr int kArriveStride = 64;   // words: one 256-B line per counter
@@ -409,38 +402,10 @@ constexpr int kMaxBpcRun = 256;  // blocks per channel of the persistent kernel
 // blocks per CU; 192 blocks of 24-sample lanes = 1.18 M samples per step)
 constexpr int run_bpc_cap(int ntaps) { return ntaps > 3 ? 192 : kMaxBpcRun; }
 constexpr int kMaxVpb = 16;      // virtual blocks per resident block of the persistent kernel
-// lane_correlate's capture queue (A/B knob): 0 = every tap's prefix read after every 8-sample
-// subgroup (the default: the queue measured 8-16 % slower at 11 taps and 8 % at 3,
-// profiles/r05_ab_cfg5_variants.txt); 1 = the queue above 3 taps (<= 3 taps: register capture,
-// lane_boundaries below)
-#ifndef GNSS_QCAP
-#define GNSS_QCAP 0
-#endif
 // the persistent loop's tap window (lane_correlate): tap offsets (+ prompt post) within this
 // many chips of each other, so every tap's chip at a lane's start lies in one 32-chip run
 constexpr double kTapSpan = 30.0;
-constexpr int kQcapMax = 8;      // capture-queue entries per lane (lane_correlate, the LDS slots)
 
-// The most taps whose replica boundary can fall inside one lane of M samples when the code
-// advances at most dmax chips per sample: tap s's boundaries sit where frac(t + off_s) wraps,
-// so a lane spanning (M - 1) dmax chips holds a boundary of every tap whose fractional offset
-// lies in a window of that width (taps whose offsets differ by whole chips count once each).
-inline int max_taps_in_lane(const double* taps, const double* post, int n, int M, double dmax)
-{
-    const double w = (M - 1) * dmax + 1e-9;
-    int best = 0;
-    for (int a = 0; a < n; a++) {
-        const double x = taps[a] + (post ? post[a] : 0.0);
-        int c = 0;
-        for (int b = 0; b < n; b++) {
-            double f = (taps[b] + (post ? post[b] : 0.0)) - x;
-            f -= floor(f);
-            if (f < w || f > 1.0 - 1e-9) c++;
-        }
-        best = c > best ? c : best;
-    }
-    return best;
-}
 // The most distinct boundary samples a lane of M samples can hold (gnss_lane_boundaries): taps
 // whose offsets differ by whole chips share a boundary and count once; the sets whose fractional
 // offsets fall in one window of the lane's (M - 1) dmax chips each bring a sample, plus one for
@@ -491,19 +456,9 @@ inline int regcap_mask(const TrkParams& p, double dmax, int64_t force)
         if (force == 2 || lane_boundaries(p.taps, p.tap_post, p.ntaps, 8 * sub, dmax) <= kRegCapMax) m |= 1 << sub;
     return m;
 }
-// The persistent kernel's 16-B hand-off granules per channel. 3 taps: [2 (step parity)]
-// [kMaxBpcRun][6]. Above 3 taps only the loop's E/P/L go through the step's exchange
-// ([2][kMaxBpcRun][<= 6], region A); the other taps' partials (region B) are published after
-// them and summed one step later by their owner blocks: [kDeferSlots (step mod 4)]
-// [value < 2 ntaps][kMaxBpcRun]. Four slots: a block can run at most two steps ahead of the
-// owner that still reads a slot.
-constexpr int kDeferSlots = 4;
-constexpr int gran_region_b(int ntaps) { return ntaps > 3 ? 2 * kMaxBpcRun * 6 : 0; }
-constexpr int gran_slot_b(int ntaps) { return 2 * ntaps * kMaxBpcRun; }
-constexpr int gran_per_chan(int ntaps)
-{
-    return ntaps > 3 ? gran_region_b(ntaps) + kDeferSlots * gran_slot_b(ntaps) : 2 * kMaxBpcRun * 2 * ntaps;
-}
+// The persistent kernel's 16-B hand-off granules per channel: [2 (step parity)][kMaxBpcRun]
+// [2 ntaps], every tap's block partials through the step's one exchange.
+constexpr int gran_per_chan(int ntaps) { return 2 * kMaxBpcRun * 2 * ntaps; }
 constexpr int kDescWords = (int)(sizeof(StepDesc) / 4);
 
 // ----------------------------------------------------------------------------

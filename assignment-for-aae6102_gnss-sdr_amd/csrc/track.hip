@@ -109,7 +109,7 @@ __device__ __forceinline__ unsigned long long load_agent(const unsigned long lon
 // runs in the persistent loop).
 struct TailK {
     double Fs, inv_Fs, codelength, S, codeFreqBasis, ms;
-    double dll_r, dll_t1, dll_t10, pll_r, pll_t1, pll_t10, tau1code, tau1carr, qcap_dmax;
+    double dll_r, dll_t1, dll_t10, pll_r, pll_t1, pll_t10, tau1code, tau1carr, cps_max;
     int32_t exact_div, conv, given, chip_off, ntaps, iE, iP, iL, bps;
     int64_t file_len, buf_base, buf_len;
     const double* taps;
@@ -133,7 +133,7 @@ __device__ __forceinline__ TailK tail_k(const TrkParams& p)
     k.codeFreqBasis = p.codeFreqBasis; k.ms = p.ms;
     k.dll_r = p.dll_r; k.dll_t1 = p.dll_t1; k.dll_t10 = p.dll_t10;
     k.pll_r = p.pll_r; k.pll_t1 = p.pll_t1; k.pll_t10 = p.pll_t10;
-    k.tau1code = p.tau1code; k.tau1carr = p.tau1carr; k.qcap_dmax = p.qcap_dmax;
+    k.tau1code = p.tau1code; k.tau1carr = p.tau1carr; k.cps_max = p.cps_max;
     k.exact_div = p.exact_div; k.conv = p.conv; k.given = p.given; k.chip_off = p.chip_off;
     k.ntaps = p.ntaps; k.iE = p.iE; k.iP = p.iP; k.iL = p.iL; k.bps = p.bps;
     k.file_len = p.file_len; k.buf_base = p.buf_base; k.buf_len = p.buf_len;
@@ -142,7 +142,7 @@ __device__ __forceinline__ TailK tail_k(const TrkParams& p)
     launder_s(k.codeFreqBasis); launder_s(k.ms);
     launder_s(k.dll_r); launder_s(k.dll_t1); launder_s(k.dll_t10);
     launder_s(k.pll_r); launder_s(k.pll_t1); launder_s(k.pll_t10);
-    launder_s(k.tau1code); launder_s(k.tau1carr); launder_s(k.qcap_dmax);
+    launder_s(k.tau1code); launder_s(k.tau1carr); launder_s(k.cps_max);
     launder_s(k.exact_div); launder_s(k.conv); launder_s(k.given); launder_s(k.chip_off);
     launder_s(k.ntaps); launder_s(k.iE); launder_s(k.iP); launder_s(k.iL); launder_s(k.bps);
     launder_s(k.file_len); launder_s(k.buf_base); launder_s(k.buf_len);
@@ -169,15 +169,6 @@ __device__ __forceinline__ double wave_at(double kd, double f, double phi0, doub
 }
 
 // (sincos_small: gnss_internal.h, shared with the VT kernels)
-#ifndef GNSS_FAST_SINCOS
-#define GNSS_FAST_SINCOS 1
-#endif
-__device__ __forceinline__ void sincos_table(double x, double* sn, double* cs)
-{
-    if constexpr (GNSS_FAST_SINCOS) sincos_small(x, sn, cs);
-    else sincos(x, sn, cs);
-}
-
 // sin/cos of a carrier phase Wave (up to ~3e5 rad): reduced by 2*pi as a double-double
 // first (W - k*kTwoPi is exact: both are multiples of 2^-50 below 8 in magnitude), so the
 // library's small-argument path runs instead of its Payne-Hanek reduction.
@@ -186,7 +177,7 @@ __device__ __forceinline__ void sincos_wave(double W, double* sn, double* cs)
     const double k = rint(W * (1.0 / kTwoPi));
     double r = __builtin_fma(-k, kTwoPi, W);
     r = __builtin_fma(-k, kTwoPiLo, r);
-    sincos_table(r, sn, cs);
+    sincos_small(r, sn, cs);
 }
 
 // The NCO state a step is prepared from.
@@ -428,7 +419,7 @@ __device__ __forceinline__ void prepare_desc_i(const P& p, const NcoState& c, in
             // phi[m] rounds once (m*dhi is exact)
             const double ph = (double)lane * dhi + (double)lane * dlo;
             double sn, cs;
-            sincos_table(ph, &sn, &cs);
+            sincos_small(ph, &sn, &cs);
             d->phi[lane] = ph;
             d->rcs[lane] = make_double2(cs, sn);
             if (lane == 0) {
@@ -805,17 +796,9 @@ __device__ __forceinline__ void static_for(F&& f)
 #ifndef GNSS_CORR_PROBE
 #define GNSS_CORR_PROBE 0
 #endif
-#ifndef GNSS_IO_DR_WAVE
-#define GNSS_IO_DR_WAVE 2  // (A/B: the wave of block 0 that runs the remPhase role)
-#endif
-#ifndef GNSS_SWEEP_IO_ALL
-#define GNSS_SWEEP_IO_ALL 0  // (A/B: block 0's wave 1 polls after its flush, as the other blocks' do)
-#endif
-#ifndef GNSS_FLUSH_PROBE
-#define GNSS_FLUSH_PROBE 0  // (A/B probe: 1 = block 0 writes no record)
-#endif
+// (the probe bits act on the slot forms: a build with any of them has no register-capture kernels)
+constexpr bool kRegcBuilt = GNSS_CORR_PROBE == 0;
 
-// (GNSS_QCAP: gnss_internal.h)
 // The C/A code bits as the lanes hold them (lane w < 32: word w, bit i of word w = chip
 // 32 w + i of the 1023, bit set = -1) extended circularly for the tap window below: bit 31 of
 // word 31 (index 1023) = chip 0, word 32 (lane 32) = chips 1..32, word 33 = chips 33..64, so
@@ -830,15 +813,6 @@ __device__ __forceinline__ unsigned ca_bits_ext(unsigned cabits, int lane)
     return cabits;
 }
 
-#ifndef GNSS_SWP
-#define GNSS_SWP 0  // (lane_correlate: 1 / 2 = the next sample's Wave formed one sample ahead)
-#endif
-#ifndef GNSS_PHI_REG
-#define GNSS_PHI_REG 0  // (lane_correlate: 1 = the rotation basis phi[m] formed in registers)
-#endif
-#ifndef GNSS_TAPWIN
-#define GNSS_TAPWIN 1  // (A/B: 0 = per-tap colon element, scalar tap loads and two code shuffles)
-#endif
 // Register capture (REGC, the <= 3-tap forms): one unrolled sample's hand-over. Lanes whose
 // capture sample is m copy the running sum into the capture register under the exec mask
 // (three VALU issues; a compare and two 64-bit selects are five), and the running sum, the
@@ -870,16 +844,10 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
 {
     constexpr int M = 8 * SUB;
     constexpr int T = kTrkThreads;
-    // Capture queue (the persistent loop above 3 taps, where the host has checked that a lane
-    // holds at most kQcapMax distinct interior boundaries, TrkParams.qcap): a tap's prefix is
-    // the lane's running sum at its last sample before the boundary, cap. Instead of reading
-    // every tap's slot after every 8-sample subgroup (NT x SUB LDS reads and 2 NT x SUB adds),
-    // the running sum is stored at the distinct interior capture samples only (queue entry =
-    // the sample's rank among them), and each tap reads its one entry in the epilogue. The
-    // value is the same running sum, so the same bits (pre = v + 0.0 either way).
-    constexpr bool QC = RELOAD && GNSS_QCAP && NT > 3;
-    static_assert(!REGC || (NT <= 3 && !QC && GNSS_CORR_PROBE == 0 && !GNSS_SWP && !GNSS_PHI_REG),
-                  "register capture: the <= 3-tap product forms");
+    // (every tap's prefix is read from the slots after every 8-sample subgroup: a queue of the
+    // distinct capture samples measured 8-16 % slower at 11 taps and 8 % at 3,
+    // profiles/r05_ab_cfg5_variants.txt)
+    static_assert(!REGC || (NT <= 3 && GNSS_CORR_PROBE == 0), "register capture: the <= 3-tap product forms");
     if constexpr ((GNSS_CORR_PROBE & 8) != 0) {  // (probe: no correlate at all)
 #pragma unroll
         for (int s = 0; s < NT; s++) { oI[s] = 0.0; oQ[s] = 0.0; }
@@ -906,7 +874,7 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
     // code values around each tap's boundary as sign bits (bit s set: -1): a0 before it,
     // a1 after; v1 = a1 and dv = a0 - a1 are rebuilt in the epilogue (2 VGPRs, not 4*NT)
     unsigned neg0 = 0u, neg1 = 0u;
-    // Tap window (GNSS_TAPWIN, the persistent loop: descriptor and tap offsets in LDS): the
+    // Tap window (the persistent loop: descriptor and tap offsets in LDS): the
     // parts of colon_elem(col_s, kf) that no tap changes (which end of the colon kf is counted
     // from, (double)kf * d, (double)(n - 1 - kf) * d) once per lane; every tap's colon ends read
     // from LDS into vector registers (broadcast reads, no scalar round trip per tap); and the
@@ -919,7 +887,7 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
     // call in floating point or that hold the colon's middle element: they redo that tap's search
     // exactly as before (the fast path's R is fused, the exact path's is not; both give the same
     // cap wherever the fast path is used: its R lies more than 1e-6 from an integer).
-    constexpr bool TW = GNSS_TAPWIN && RELOAD && (GNSS_CORR_PROBE & 66) == 0;
+    constexpr bool TW = RELOAD && (GNSS_CORR_PROBE & 66) == 0;
     if constexpr (TW) {
         const int nn = ni - 1;
         const bool mid = 2 * kfi == nn, lower = kfi <= nn / 2;
@@ -1026,17 +994,9 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
     }
 
     double run_r = 0.0, run_i = 0.0;
-    double pre_r[QC ? 1 : NT], pre_i[QC ? 1 : NT];
-    if constexpr (!QC) {
+    double pre_r[NT], pre_i[NT];
 #pragma unroll
-        for (int s = 0; s < NT; s++) { pre_r[s] = 0.0; pre_i[s] = 0.0; }
-    }
-    unsigned cmask = 0u;  // QC: the lane's interior capture samples (0 <= cap < M - 1)
-    if constexpr (QC) {
-#pragma unroll
-        for (int s = 0; s < NT; s++)
-            if (cap[s] >= 0 && cap[s] < M - 1) cmask |= 1u << cap[s];
-    }
+    for (int s = 0; s < NT; s++) { pre_r[s] = 0.0; pre_i[s] = 0.0; }
 
     // fmt 1: I - mean(I), Q - mean(Q) per sample, as the reference forms rawsignal0DC
     double mu_r = 0.0, mu_i = 0.0;
@@ -1045,19 +1005,6 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
         mu_i = uni(dp->mu_i);
     }
 
-    // GNSS_PHI_REG: the rotation basis phi[m] = m*dhi + m*dlo formed in registers (as
-    // prepare_desc forms the table entry: the same operations, the same bits) instead of read
-    double dhi_l = 0.0, dlo_l = 0.0;
-    if constexpr (GNSS_PHI_REG) {
-        dhi_l = uni(dp->dhi);
-        dlo_l = uni(dp->dlo);
-    }
-    // GNSS_SWP (A/B knob): the next sample's exact Wave formed one sample ahead (before this
-    // sample's rotation and accumulation), so two independent dependency chains are in flight;
-    // 2 also fences each sample's instructions from the next one's (sched_barrier), so the
-    // scheduler interleaves exactly those two chains. Same operations, same bits.
-    double Wpipe = 0.0;
-    if constexpr (GNSS_SWP) Wpipe = wave_at<DIVIDE>(kb + 1.0, f, phi0, Fs, rFs);
     // REGC (<= 3 taps): no LDS slots. A tap's boundaries are a chip apart and taps a whole number
     // of chips apart share theirs, so where the host's lane_boundaries() admits this form a lane
     // has one interior capture sample, capA (the first tap's that has one), and its running sum is
@@ -1270,16 +1217,8 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
             } else if (m > 0) {
                 // w = x * (rc + i rs) * (1 + i eta): the first-order residue folded into the
                 // rotation, the products accumulated by FMA into the running sums
-                double W;
-                if constexpr (GNSS_SWP) {
-                    W = Wpipe;
-                    if (m + 1 < M) Wpipe = wave_at<DIVIDE>(kbj + (double)(mm + 1), f, phi0, Fs, rFs);
-                } else {
-                    W = wave_at<DIVIDE>(kbj + (double)mm, f, phi0, Fs, rFs);
-                }
-                double phm;
-                if constexpr (GNSS_PHI_REG) phm = (double)m * dhi_l + (double)m * dlo_l;
-                else phm = dp->phi[m];
+                const double W = wave_at<DIVIDE>(kbj + (double)mm, f, phi0, Fs, rFs);
+                const double phm = dp->phi[m];
                 const double eta = (W - Wb) - phm;
                 const double2 rcs = ld_rcs(dp, m);
                 const double rc = __builtin_fma(-eta, rcs.y, rcs.x);
@@ -1292,36 +1231,22 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
                 run_r += xr;
                 run_i += xi;
             }
-            if constexpr (QC) {
-                if ((cmask >> m) & 1u)
-                    myslot[__builtin_popcount(cmask & ((1u << m) - 1u)) * T] = make_double2(run_r, run_i);
-            } else {
-                myslot[mm * T] = make_double2(run_r, run_i);
-            }
-            if constexpr (GNSS_SWP == 2) __builtin_amdgcn_sched_barrier(0);
+            myslot[mm * T] = make_double2(run_r, run_i);
         }
-        if constexpr (!QC) {
 #pragma unroll
-            for (int s = 0; s < NT; s++) {
-                const unsigned idx = (unsigned)(cap[s] - 8 * j);
-                const double2 v = *(idx < 8u ? myslot + idx * T : zero);
-                pre_r[s] += v.x;
-                pre_i[s] += v.y;
-            }
+        for (int s = 0; s < NT; s++) {
+            const unsigned idx = (unsigned)(cap[s] - 8 * j);
+            const double2 v = *(idx < 8u ? myslot + idx * T : zero);
+            pre_r[s] += v.x;
+            pre_i[s] += v.y;
         }
     };
-#ifndef GNSS_UNROLL_TAPS
-#define GNSS_UNROLL_TAPS 0  // (A/B: 1 = the > 3-tap subgroup loop unrolled like the 3-tap one)
-#endif
     if constexpr (REGC) {
         // (above)
-    } else if constexpr (RELOAD && NT > 3 && !GNSS_UNROLL_TAPS) {
+    } else if constexpr (RELOAD && NT > 3) {
         // descriptor in LDS: one subgroup at a time (unrolled, the compiler would keep
         // every subgroup's table values live)
 #pragma unroll 1
-        for (int j = 0; j < SUB; j++) subgroup(j);
-    } else if constexpr (RELOAD) {
-#pragma unroll
         for (int j = 0; j < SUB; j++) subgroup(j);
     } else {
 #pragma unroll
@@ -1335,19 +1260,8 @@ __device__ __forceinline__ void lane_correlate(const TrkParams& p, const Desc* d
         const double a0 = ((neg0 >> s) & 1u) ? -1.0 : 1.0;
         const double v1 = ((neg1 >> s) & 1u) ? -1.0 : 1.0;
         const double dv = a0 - v1;
-        double pr, pi;
-        if constexpr (QC) {
-            const int cs = cap[s];
-            const int q = __builtin_popcount(cmask & ((1u << (cs > 0 ? cs : 0)) - 1u));
-            const double2 v = myslot[(q < 8 ? q : 7) * T];  // (read even where unused: no divergence)
-            pr = (cs < 0 ? 0.0 : cs == M - 1 ? run_r : v.x) + 0.0;
-            pi = (cs < 0 ? 0.0 : cs == M - 1 ? run_i : v.y) + 0.0;
-        } else {
-            pr = pre_r[s];
-            pi = pre_i[s];
-        }
-        const double ur = __builtin_fma(dv, pr, v1 * run_r);
-        const double ui = __builtin_fma(dv, pi, v1 * run_i);
+        const double ur = __builtin_fma(dv, pre_r[s], v1 * run_r);
+        const double ui = __builtin_fma(dv, pre_i[s], v1 * run_i);
         oI[s] = __builtin_fma(cb, ui, sb * ur);
         oQ[s] = __builtin_fma(cb, ur, -(sb * ui));
     }
@@ -1384,106 +1298,21 @@ __device__ __forceinline__ void lds_barrier()
 // above, in the per-step kernel, two passes of half the taps each, so the reduction's LDS
 // (2 * taps * (T + 32) doubles) stays small and the one-pass form's extra registers (98 -> 129
 // VGPRs at 11 taps) do not cut that kernel's occupancy. The persistent kernel reduces up to
-// GNSS_RED_ONEPASS taps in one pass: its 11-tap forms run two blocks per CU (their VGPRs),
+// kRedOnePass taps in one pass: its 11-tap forms run two blocks per CU (their VGPRs),
 // where the one-pass slots still fit (59-71 KB of LDS a block). Every value is reduced by the
 // same lanes in the same order whichever pass it is in (same bits).
-#ifndef GNSS_RED_ONEPASS
-#define GNSS_RED_ONEPASS 11
-#endif
+// (A wave-level DPP tree with one barrier instead of three measured slower -- block partial
+// 0.48 -> 0.68 us, 203 -> 217 ms at 32 channels x 11 taps -- and its other order moves the
+// full-length goldens' tie flips: profiles/r05_ab_block_tree.txt.)
+constexpr int kRedOnePass = 11;
 template <int NT> constexpr int red_taps() { return NT > 3 ? (NT + 1) / 2 : NT; }
-template <int NT> constexpr int run_red_taps() { return NT <= GNSS_RED_ONEPASS ? NT : red_taps<NT>(); }
+template <int NT> constexpr int run_red_taps() { return NT <= kRedOnePass ? NT : red_taps<NT>(); }
 template <int HT> constexpr int red_words() { return 2 * HT * (kTrkThreads + 32); }
-
-// GNSS_RED 1 (round 5, A/B knob, off): each value summed over a wave without LDS -- the DPP
-// butterfly over quads, half rows and rows (every lane of a row ends with the row's sum, the
-// same bits in each: IEEE addition commutes), the four rows' sums read from lanes 0 / 16 / 32 /
-// 48 and added as (r0 + r1) + (r2 + r3) -- then the four waves' sums through LDS as
-// (w0 + w1) + (w2 + w3). One barrier instead of three, but 8 lane reads per value: measured
-// slower (block partial 0.48 -> 0.68 us; 10-ms launch 36.8-37.0 -> 37.8-38.0 ms at 3 taps,
-// 203 -> 217 ms at 32 channels x 11 taps; profiles/r05_ab_block_tree.txt). A different order
-// also moves the last bits, so the full-length goldens' tie flips move (config 3 channel 5
-// parts at step 3 944 with it). GNSS_RED 2 combines the rows by DPP broadcasts instead of
-// lane reads (same bits as 1): +1 % at 3 taps, equal at 11.
-#ifndef GNSS_RED
-#define GNSS_RED 0
-#endif
-// a double read from one lane (the result is uniform)
-__device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-// a double moved across lanes by a DPP control with a row mask; lanes of disabled rows get 0
-template <int CTRL, int ROWS>
-__device__ __forceinline__ double dpp_f64_rows(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROWS, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROWS, 0xF, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-// one value's sum over the wave's 64 lanes in the fixed order above (every lane active)
-__device__ __forceinline__ double wave_sum(double a)
-{
-    if constexpr (GNSS_RED == 2) {
-        // (GNSS_RED 2: the rows combined by DPP broadcasts instead of lane reads -- row 1 +=
-        // row 0 and row 3 += row 2 (row_bcast:15), then rows 2, 3 += row 1 (row_bcast:31): lane
-        // 63 ends with (r3 + r2) + (r1 + r0); the other lanes' values are not used)
-        a += dpp_f64<0xB1>(a);
-        a += dpp_f64<0x4E>(a);
-        a += dpp_f64<0x141>(a);
-        a += dpp_f64<0x140>(a);
-        a += dpp_f64_rows<0x142, 0xA>(a);
-        a += dpp_f64_rows<0x143, 0xC>(a);
-        return a;
-    }
-    a += dpp_f64<0xB1>(a);   // quad_perm [1,0,3,2]
-    a += dpp_f64<0x4E>(a);   // quad_perm [2,3,0,1]
-    a += dpp_f64<0x141>(a);  // row_half_mirror: the other quad of the 8
-    a += dpp_f64<0x140>(a);  // row_mirror: the other 8 of the 16
-    return (readlane_f64(a, 0) + readlane_f64(a, 16)) + (readlane_f64(a, 32) + readlane_f64(a, 48));
-}
-
-// the waves' sums of the values of mask `sel` (pass value w = the w-th selected I / Q), combined:
-// value w in lanes 4w .. 4w + 3 on return; s_mem free on entry and on return
-template <int NT>
-__device__ __forceinline__ double block_tree(double* s_mem, const double (&oI)[NT], const double (&oQ)[NT],
-                                             int tid, unsigned sel)
-{
-    constexpr int NV = 2 * NT;
-    const int wv = tid >> 6, lane = tid & 63;
-    double* ws = s_mem;  // [4][NV]
-    int w = 0;
-#pragma unroll
-    for (int s = 0; s < NT; s++) {
-        if ((sel >> s) & 1u) {  // (sel uniform)
-            const double si = wave_sum(oI[s]), sq = wave_sum(oQ[s]);
-            if (lane == (GNSS_RED == 2 ? 63 : 0)) {
-                ws[wv * NV + 2 * w] = si;
-                ws[wv * NV + 2 * w + 1] = sq;
-            }
-            w++;
-        }
-    }
-    lds_barrier();
-    double a = 0.0;
-    if (tid < 2 * w * 4) {
-        const int v = tid >> 2;
-        a = (ws[v] + ws[NV + v]) + (ws[2 * NV + v] + ws[3 * NV + v]);
-    }
-    lds_barrier();  // ws read before the caller reuses s_mem
-    return a;
-}
 
 template <int NT, int HT = red_taps<NT>()>
 __device__ __forceinline__ double block_partial(double* s_mem, const double (&oI)[NT],
                                                 const double (&oQ)[NT], int tid)
 {
-    if constexpr (GNSS_RED) return block_tree<NT>(s_mem, oI, oQ, tid, (1u << NT) - 1u);
     constexpr int T = kTrkThreads;
     double* red = s_mem;                 // [2 HT][T]
     double* red2 = s_mem + 2 * HT * T;   // [2 HT][32]
@@ -1525,51 +1354,6 @@ __device__ __forceinline__ double block_partial(double* s_mem, const double (&oI
     return a;
 }
 
-// One pass of block_partial over a chosen set of taps (the persistent loop's split of the
-// > 3-tap reduction: the loop's E/P/L first, the other taps after their publication). The
-// taps of bit mask `sel` (at most HT of them) take part in tap order: the q-th
-// one's I / Q are the pass's values 2q / 2q + 1, reduced by exactly block_partial's lanes and
-// order (8-lane runs, four runs per lane, the DPP quad butterfly), so every value has the bits
-// block_partial gives it. Value w of the pass ends in lanes 4w .. 4w + 3.
-template <int NT, int HT>
-__device__ __forceinline__ double block_pass(double* s_mem, const double (&oI)[NT], const double (&oQ)[NT],
-                                             int tid, unsigned sel)
-{
-    if constexpr (GNSS_RED) return block_tree<NT>(s_mem, oI, oQ, tid, sel);
-    constexpr int T = kTrkThreads;
-    double* red = s_mem;                 // [2 HT][T]
-    double* red2 = s_mem + 2 * HT * T;   // [2 HT][32]
-#pragma unroll
-    for (int s = 0; s < NT; s++) {
-        if ((sel >> s) & 1u) {  // (sel wave-uniform: scalar branches)
-            const int q = __builtin_popcount(sel & ((1u << s) - 1u));
-            red[(2 * q) * T + tid] = oI[s];
-            red[(2 * q + 1) * T + tid] = oQ[s];
-        }
-    }
-    lds_barrier();
-    const int nv = 2 * __builtin_popcount(sel);
-    for (int e = tid; e < nv * 32; e += T) {
-        const double* r = red + (e >> 5) * T + (e & 31) * 8;
-        double x = r[0];
-#pragma unroll
-        for (int k = 1; k < 8; k++) x += r[k];
-        red2[e] = x;
-    }
-    lds_barrier();
-    double a = 0.0;
-    if (tid < nv * 4) {
-        const double* r = red2 + (tid >> 2) * 32 + (tid & 3) * 8;
-        a = r[0];
-#pragma unroll
-        for (int k = 1; k < 8; k++) a += r[k];
-        a += dpp_f64<0xB1>(a);  // quad_perm [1,0,3,2]
-        a += dpp_f64<0x4E>(a);  // quad_perm [2,3,0,1]
-    }
-    lds_barrier();  // red / red2 read before the next pass or the caller reuses the slots
-    return a;
-}
-
 // Channel: the sum over the bpc block partials of value v = tid / L (tid < L*NV, L = 16
 // lanes per value where 16*NV fits the block, else 8): lane q = tid % L adds blocks q,
 // q+L, ... in order, then a DPP butterfly over the L lanes. Every lane of the L returns the
@@ -1577,22 +1361,6 @@ __device__ __forceinline__ double block_pass(double* s_mem, const double (&oI)[N
 template <int NV> constexpr int chan_lanes()
 {
     return 16 * NV <= kTrkThreads ? 16 : 8 * NV <= kTrkThreads ? 8 : 4;  // (25 taps: 4)
-}
-
-// The same sum with the lane count L given (the persistent loop's deferred taps keep the L
-// of the whole tap set, chan_lanes<2 NT>(), whatever subset of values it sums at once).
-template <int L, class Load>
-__device__ __forceinline__ double channel_sum_l(int bpc, int tid, Load load)
-{
-    const int v = tid / L, q = tid % L;
-    double a = 0.0;
-#pragma unroll 4
-    for (int k = q; k < bpc; k += L) a += load(k, v);
-    a += dpp_f64<0xB1>(a);   // quad_perm [1,0,3,2]
-    a += dpp_f64<0x4E>(a);   // quad_perm [2,3,0,1]
-    if constexpr (L >= 8) a += dpp_f64<0x141>(a);   // row_half_mirror: the other quad of the 8
-    if constexpr (L == 16) a += dpp_f64<0x140>(a);  // row_mirror: the other 8 of the 16
-    return a;
 }
 
 template <int NV, class Load>
@@ -1863,11 +1631,9 @@ __device__ bool sweep_words(const unsigned long long* g, int n, unsigned tag, un
 
 // (16-B granules {lo, tag, hi, tag}, publish16: gnss_internal.h, shared with the VT loop)
 // granule loads a poller keeps in flight per batch: one at a time for E / P / L (2-3 granules a
-// poller, where batching measured 1 % slower), GNSS_SWEEP_BATCH above 3 taps (8-11 a poller: the
+// poller, where batching measured 1 % slower), kSweepBatch above 3 taps (8-11 a poller: the
 // 11-tap 4-channel launch 49.5 -> 45.9 ms at 4, profiles/r06_ab_sweep_batch.txt)
-#ifndef GNSS_SWEEP_BATCH
-#define GNSS_SWEEP_BATCH 4
-#endif
+constexpr int kSweepBatch = 4;
 
 // Poll n 16-B granules until both tags of each equal `tag`; granule e's words land in
 // dst[2e], dst[2e+1]. Same protocol as sweep_words (pollers pid 0..np-1, n <= 64*np).
@@ -1905,7 +1671,6 @@ __device__ bool sweep16(__amdgpu_buffer_rsrc_t r, int n, unsigned tag, unsigned*
                 }
         }
         if (!todo) break;
-        if constexpr (GNSS_XCHG_SLEEP > 0) __builtin_amdgcn_s_sleep(GNSS_XCHG_SLEEP);  // (A/B knob)
         if (++late >= 64) {
             const unsigned long long t = wall_clock64();
             if (!t0) t0 = t;
@@ -1925,52 +1690,6 @@ __device__ bool sweep16(__amdgpu_buffer_rsrc_t r, int n, unsigned tag, unsigned*
     unsigned v = 0;
 #pragma unroll
     for (int w = 0; w < kTrkThreads / 64; w++) v |= s_vote[w];
-    return v == 0;
-}
-
-// sweep16 over two granule ranges at once (the persistent loop's > 3-tap form: this step's
-// E/P/L partials, plus in the blocks that own deferred taps the previous step's partials of
-// those taps). Logical granule e < n1 is base1 + e (tag1, words to dst1[2e]); e >= n1 is
-// base2 + e - n1 (tag2, dst2). Same pollers, bound and closing vote as sweep16.
-__device__ bool sweep16x2(__amdgpu_buffer_rsrc_t r, int n1, int base1, unsigned tag1, unsigned* dst1, int n2,
-                          int base2, unsigned tag2, unsigned* dst2, int pid, int np, unsigned* err)
-{
-    const int n = n1 + n2;
-    unsigned long long todo = 0;
-    if (pid >= 0)
-        for (int k = 0, e = pid; e < n; k++, e += np) todo |= 1ull << k;
-    unsigned long long t0 = 0;
-    int late = 0;
-    while (todo) {
-        for (int k = 0; (todo >> k) != 0; k++) {
-            if (!((todo >> k) & 1ull)) continue;
-            const int e = pid + k * np;
-            const bool first = e < n1;
-            const int e2 = first ? e : e - n1;
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, ((first ? base1 : base2) + e2) * 16, 0, kPolSc1);
-            const unsigned tg = first ? tag1 : tag2;
-            if (v.y == tg && v.w == tg) {
-                unsigned* d = first ? dst1 : dst2;
-                d[2 * e2] = v.x;
-                d[2 * e2 + 1] = v.z;
-                todo &= ~(1ull << k);
-            }
-        }
-        if (!todo) break;
-        if (++late >= 64) {
-            const unsigned long long t = wall_clock64();
-            if (!t0) t0 = t;
-            else if (t - t0 > 200000000ull) { atomicExch(err, 1u); break; }
-            late = 0;
-        }
-    }
-    __shared__ unsigned s_vote2[kTrkThreads / 64];
-    const unsigned any_left = __ballot(todo != 0) != 0ull ? 1u : 0u;
-    if ((threadIdx.x & 63) == 0) s_vote2[threadIdx.x >> 6] = any_left;
-    lds_barrier();
-    unsigned v = 0;
-#pragma unroll
-    for (int w = 0; w < kTrkThreads / 64; w++) v |= s_vote2[w];
     return v == 0;
 }
 
@@ -2022,14 +1741,9 @@ __device__ __forceinline__ void prefetch_raw(const int8_t* iq, int64_t g0, int64
 // (the same fp64 code on the same sums: bit-identical copies), so a step needs one
 // exchange only: each block publishes its partial sums and reads everyone's. Block 0
 // of the channel writes the records, C/N0 and, at the end, the state.
-#ifndef GNSS_DEFER
-#define GNSS_DEFER 0  // (A/B: 0 = every tap through the step's exchange, the round-4 form)
-#endif
-#ifndef GNSS_WPE_TAPS
-#define GNSS_WPE_TAPS 2  // (A/B: waves per EU of the > 3-tap persistent forms; 3 = three blocks per CU)
-#endif
+// (waves per EU: three blocks per CU at <= 3 taps, two above)
 template <int NT, int SUB, bool DIVIDE, bool VB = false, bool REGC = false>
-__global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT > 3 ? GNSS_WPE_TAPS : 3, NT > 3 ? GNSS_WPE_TAPS : 3))) void track_run_kernel(const TrkParams* __restrict__ pp,
+__global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT > 3 ? 2 : 3, NT > 3 ? 2 : 3))) void track_run_kernel(const TrkParams* __restrict__ pp,
                                                                const TrkBuffers* __restrict__ bp, int bpc,
                                                                int vpb, int nsteps, unsigned tag0)
 {
@@ -2047,16 +1761,8 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
     // one-block-per-block form, the loop compiled away -- the headline's 8 channels.)
     const int vpb_ = VB ? vpb : 1;
     const int pbpc = (bpc + vpb_ - 1) / vpb_;
-    // (A/B knob GNSS_XCD_LOCAL: with 8 channels, channel = the block's XCD (blocks are dealt
-    // round-robin over the 8 XCDs), so a channel's exchange stays in one L2)
-    // (GNSS_XCD_LOCAL 2, the control experiment: with 8 channels x 96 blocks, a CU's three
-    // blocks b, b + 256, b + 512 (profiles/r03_channel_lockstep.txt) are one channel's, as
-    // XCD-local placement makes them, but each channel's 32 CUs span all 8 XCDs)
-    const bool xl = GNSS_XCD_LOCAL == 1 && !VB && p.nch == 8;
-    const bool cul = GNSS_XCD_LOCAL == 2 && !VB && p.nch == 8 && pbpc == 96;
-    const int ch = xl ? (int)(blockIdx.x & 7) : cul ? (int)((blockIdx.x & 255) >> 5) : (int)(blockIdx.x / pbpc);
-    const int pblk = xl ? (int)(blockIdx.x >> 3)
-                    : cul ? (int)((blockIdx.x & 31) * 3 + (blockIdx.x >> 8)) : (int)(blockIdx.x - ch * pbpc);
+    const int ch = (int)(blockIdx.x / pbpc);
+    const int pblk = (int)(blockIdx.x - ch * pbpc);
     const int blk = pblk * vpb_;
     const int nvb = VB ? (bpc - blk < vpb_ ? bpc - blk : vpb_) : 1;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -2065,19 +1771,7 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
     constexpr int kSlot = REGC ? 0 : 8 * T * 2;       // running sums [8][T] double2 (register capture: none)
     constexpr int kRed = red_words<run_red_taps<NT>()>();  // block reduction
     constexpr int kPart = run_bpc_cap(NT) * NV;       // everyone's partials (as words)
-    // Above 3 taps only E / P / L cross the step's exchange (kDefer, below); GNSS_DEFER 2 (one
-    // block of the step per resident block) has one wave reduce the other taps' block partials
-    // while the rest poll: their lane values staged at s_mem + kPwD, [value][T], and that wave's
-    // run sums after them. The exchange's words then need bpc * (E/P/L values + owned values).
-    constexpr bool kDefer = GNSS_DEFER && NT > 3;
-    constexpr bool kWave1 = GNSS_DEFER == 2 && kDefer && !VB;
-    // (defer_reduce restates the round-4 block order for its one wave)
-    static_assert(!kWave1 || GNSS_RED == 0, "GNSS_DEFER 2 needs GNSS_RED 0");
-    constexpr int kPwD = run_bpc_cap(NT) * 8 + 2 * NT;  // (pbpc = bpc: own_n <= nBv / bpc + 1)
-    constexpr int kStage = 2 * (NT - 1) * T;
-    constexpr int kMemW = kWave1 ? kPwD + kStage + 2 * NT * 32 : 0;
-    constexpr int kMem1 = kSlot > kRed ? kSlot : kRed;
-    constexpr int kMem0 = kMem1 > kMemW ? kMem1 : kMemW;
+    constexpr int kMem0 = kSlot > kRed ? kSlot : kRed;
     constexpr int kMem = kMem0 > kPart + 16 * NV ? kMem0 : kPart + 16 * NV;
     __shared__ __attribute__((aligned(16))) double s_mem[kMem];
     __shared__ __attribute__((aligned(16))) int4 s_raw[SUB * T];   // this step's IF
@@ -2097,90 +1791,14 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
     const int64_t gmax = (p.buf_base + p.buf_len) / 16 - 1;  // last resident 16-B group
     // (circularly extended for lane_correlate's tap window, ca_bits_ext)
     const unsigned cabits = ca_bits_ext(lane < 32 ? ((g_cu32*)b.ca_bits)[ch * 32 + lane] : 0u, lane);
-    // this channel's granules (gran_per_chan): 3 taps [parity][block][value] x 16 B; above,
-    // region A [parity][block][E/P/L value] and region B [step mod 4][value][block]
+    // this channel's granules (gran_per_chan): [step parity][block][value] x 16 B. Every tap goes
+    // through the step's one exchange: only E / P / L there and the other taps a step later
+    // measured 2.5-10 % slower at 11 taps (profiles/r06_ab_defer_onepass.txt)
     const __amdgpu_buffer_rsrc_t pg = __builtin_amdgcn_make_buffer_rsrc(
         b.pgran + (int64_t)ch * 2 * gran_per_chan(NT), (short)0, gran_per_chan(NT) * 16, kBufRsrcWord3);
     constexpr int kChanWords = (int)(sizeof(TrkChan) / 8);
-
-    // Above 3 taps (config 5's 11-tap ACF) only E / P / L feed the loop (trackingCT.m:470-483):
-    // they are reduced, published and swept first (region A); the other taps' values (B,
-    // only when the caller asked for the taps) are reduced after that publication, overlapping
-    // the exchange, and the previous step's are swept beside this step's E/P/L by the blocks
-    // that own them (a run of B values per block, blocks 4, 5, ...), whose idle tail wave
-    // sums them and writes the taps one step late. Every value keeps its reduction lanes and
-    // order (block_pass, channel_sum_l with the whole tap set's lane count), so the records
-    // and taps are the bits of the one-exchange form and of the per-step kernel.
     constexpr int CL = chan_lanes<NV>();
     constexpr int HT = run_red_taps<NT>();
-    // The configuration lives in LDS and is read where it is used (volatile LDS loads, never
-    // hoisted into registers that would live across the step loop: this kernel is at its
-    // register budget). selA / selB: the loop's taps / the others; NA: E/P/L values; nBv: B
-    // values; hb: B taps per reduction pass; [own_lo, own_lo + own_n): this block's B values;
-    // bslot / bneg (wave 1): the slot and phase-C sign of the step whose B values are due.
-    struct DeferCfg {
-        unsigned selA, selB;
-        int NA, nBv, hb, own_lo, own_n, bneg;
-        int64_t bslot;
-        int vmap[kDefer ? NV : 1];  // A values, then B values -> value index 2 tap + I/Q
-    };
-    __shared__ DeferCfg s_df;
-    typedef __attribute__((address_space(3))) volatile const int lds_vint;
-    typedef __attribute__((address_space(3))) volatile const long long lds_vi64;
-    auto dfi = [&](const int& f) { return uni((int)*(lds_vint*)&f); };
-    auto NA_ = [&]() { return kDefer ? dfi(s_df.NA) : NV; };
-    auto own_n_ = [&]() { return kDefer ? dfi(s_df.own_n) : 0; };
-    const bool dob = kDefer && b.taps_rec != nullptr;
-    if constexpr (kDefer) {
-        if (tid == 0) {
-            unsigned selA = 0, selB = 0;
-            for (int s = 0; s < NT; s++) {
-                if (s == tk.iE || s == tk.iP || s == tk.iL) selA |= 1u << s;
-                else selB |= 1u << s;
-            }
-            const int nA = __builtin_popcount(selA), nB = __builtin_popcount(selB);
-            const int nBv = 2 * nB, npass = (nB + HT - 1) / HT;
-            int own_lo = 0, own_n = 0;
-            if (dob && nBv > 0) {  // this block's run of B values
-                const int c = (nBv + pbpc - 1) / pbpc;
-                const int nown = (nBv + c - 1) / c;
-                const int r = ((pblk - 4) % pbpc + pbpc) % pbpc;
-                if (r < nown) {
-                    own_lo = r * c;
-                    own_n = nBv - own_lo < c ? nBv - own_lo : c;
-                }
-            }
-            s_df.selA = selA;
-            s_df.selB = selB;
-            s_df.NA = 2 * nA;
-            s_df.nBv = nBv;
-            s_df.hb = npass > 0 ? (nB + npass - 1) / npass : 1;
-            s_df.own_lo = own_lo;
-            s_df.own_n = own_n;
-            s_df.bneg = 0;
-            s_df.bslot = 0;
-            for (int s = 0; s < NT; s++) {
-                const unsigned below = (1u << s) - 1u;
-                const int v = ((selA >> s) & 1u) ? 2 * __builtin_popcount(selA & below)
-                                                 : 2 * nA + 2 * __builtin_popcount(selB & below);
-                s_df.vmap[v] = 2 * s;
-                s_df.vmap[v + 1] = 2 * s + 1;
-            }
-        }
-    }
-    // B taps of pass ps (1-based): ranks (ps - 1) * hb .. ps * hb - 1 among the B taps
-    auto sel_pass = [&](int ps) {
-        const unsigned selB = (unsigned)dfi(*(const int*)&s_df.selB);
-        const int hb = dfi(s_df.hb);
-        unsigned m = 0u;
-        int r = 0;
-        for (int s = 0; s < NT; s++)
-            if ((selB >> s) & 1u) {
-                if (r >= (ps - 1) * hb && r < ps * hb) m |= 1u << s;
-                r++;
-            }
-        return m;
-    };
 
     // step 0's descriptor and the state, as the previous launch left them
     for (int e = tid; e < kDescWords; e += T)
@@ -2202,10 +1820,7 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
     const bool dio = pblk == duty_a;  // the block holding the record's part 1
     // blocks whose wave 1 flush is long (record part 1; part 2 and the tap record, ~1 us against
     // ~0.5 elsewhere, profiles/r05_stamps_1ms.txt) poll with waves 0, 2, 3 only
-#ifndef GNSS_DSW_B
-#define GNSS_DSW_B 1  // (A/B: 0 = only the part-1 block polls without wave 1)
-#endif
-    const bool dsw = dio || (GNSS_DSW_B && pblk == duty_b);
+    const bool dsw = dio || pblk == duty_b;
     // (that block's wave 1, lane 0: dvpre[s_c.nstep], the running delayValue prefix its flushes
     // extend -- no read-back of its own stores)
     int64_t dvrun = 0;
@@ -2220,74 +1835,9 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
     // The pending step's side effects, by wave 1 while the next step's partials are in
     // flight (off the critical path): the state replica (every block, in place) and, in the
     // duty blocks above, the record, C/N0 and taps.
-    int s_now = 0;  // (probe stamps of the flush)
-    // the owned B values of a finished step, swept into pb: summed (8 lanes per value, the
-    // order of channel_sum<NV>) and written to the taps, by one wave
-    auto defer_write = [&](const unsigned* pb) {
-        constexpr int VPW = 64 / CL;  // values per wave pass
-        const int own_n = own_n_(), own_lo = dfi(s_df.own_lo), NA = NA_(), bneg = dfi(s_df.bneg);
-        const int64_t bslot = uni((int64_t)*(lds_vi64*)&s_df.bslot);
-        for (int c0 = 0; c0 < own_n; c0 += VPW) {
-            const double a = channel_sum_l<CL>(bpc, lane, [&](int k, int vl) {
-                const int vv = c0 + vl;
-                if (vv >= own_n) return 0.0;
-                const unsigned lo = pb[(vv * bpc + k) * 2], hi = pb[(vv * bpc + k) * 2 + 1];
-                return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-            });
-            const int vv = c0 + lane / CL;
-            if (lane % CL == 0 && vv < own_n && bslot < p.rec_cap)
-                ((g_dbl*)b.taps_rec)[((int64_t)ch * p.rec_cap + bslot) * NV + s_df.vmap[NA + own_lo + vv]] =
-                    bneg ? -a : a;  // (phase C: negated like every tap, :447-449)
-        }
-    };
-    // after a launch's last flush: the owned B values of finished step sf, swept and written
-    auto defer_final = [&](int sf) {
-        if (!kDefer || sf < 0) return;
-        const int own_n = own_n_();  // (block-uniform)
-        if (own_n <= 0) return;
-        unsigned* pb = reinterpret_cast<unsigned*>(s_mem);
-        if (!sweep16x2(pg, 0, 0, 0u, pb, own_n * bpc,
-                       gran_region_b(NT) + (sf & 3) * gran_slot_b(NT) + dfi(s_df.own_lo) * bpc, tag0 + sf + 1, pb,
-                       tid, T, b.run_err))
-            return;
-        if (wv == 1) defer_write(pb);
-    };
-    // GNSS_DEFER 2: one wave's reduction of the staged other-tap lane values of step `step`,
-    // exactly block_partial's order per value (8-lane runs in order, four runs per lane, the
-    // DPP quad butterfly), published to region B
-    auto defer_reduce = [&](int step) {
-        const double* stg = s_mem + kPwD;
-        double* r2 = s_mem + kPwD + kStage;  // [value][32] run sums
-        const int nbv = dfi(s_df.nBv);
-        for (int e = lane; e < nbv * 32; e += 64) {
-            const double* r = stg + (e >> 5) * T + (e & 31) * 8;
-            double x = r[0];
-#pragma unroll
-            for (int k = 1; k < 8; k++) x += r[k];
-            r2[e] = x;
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the run sums are in LDS (this wave's)
-        double a = 0.0;
-        if (lane < nbv * 4) {
-            const double* r = r2 + (lane >> 2) * 32 + (lane & 3) * 8;
-            a = r[0];
-#pragma unroll
-            for (int k = 1; k < 8; k++) a += r[k];
-            a += dpp_f64<0xB1>(a);  // quad_perm [1,0,3,2]
-            a += dpp_f64<0x4E>(a);  // quad_perm [2,3,0,1]
-            if ((lane & 3) == 0)
-                publish16(pg, gran_region_b(NT) + (step & 3) * gran_slot_b(NT) + (lane >> 2) * bpc + blk, a,
-                          tag0 + step + 1);
-        }
-    };
     auto flush = [&]() {
         if (wv == 1) {
-            // (probe GNSS_FLUSH_PROBE & 2: block 0's record part twice, stamped at [2000..2002]
-            // of the step's row: cold, then warm)
-            unsigned long long* fr = kProbe && (GNSS_FLUSH_PROBE & 2) && b.stamps && ch == 0 && io && lane == 0
-                                         ? b.stamps + (size_t)(s_now % kStampSlots) * kStampRow : nullptr;
-            if (fr) fr[2000] = wall_clock64();
-            if (lane == 0 && !(GNSS_FLUSH_PROBE & 1)) {
+            if (lane == 0) {
                 if (dio) {
                     if (!pre_ok) {  // (a launch's last flush: the column's prefix read here)
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2301,20 +1851,8 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
                 }
                 else if (pblk == duty_b) write_record_i(p, b, ch, s_c, s_o, s_u, s_fin, nullptr, 2);
             }
-            if (fr) {
-                fr[2001] = wall_clock64();
-                write_record_i(p, b, ch, s_c, s_o, s_u, s_fin, pre, 3);
-                fr[2002] = wall_clock64();
-            }
-            if (pblk == duty_b && b.taps_rec && lane < NA_() && s_c.slot < p.rec_cap) {
-                // (above 3 taps the loop's values only: the others follow a step later, defer_write)
-                const int v = kDefer ? s_df.vmap[lane] : lane;
-                ((g_dbl*)b.taps_rec)[((int64_t)ch * p.rec_cap + s_c.slot) * NV + v] = s_fin[v];
-            }
-            if (kDefer && lane == 0) {  // the pending step's slot and sign, for its deferred taps
-                s_df.bslot = s_c.slot;
-                s_df.bneg = s_o.phaseC;
-            }
+            if (pblk == duty_b && b.taps_rec && lane < NV && s_c.slot < p.rec_cap)
+                ((g_dbl*)b.taps_rec)[((int64_t)ch * p.rec_cap + s_c.slot) * NV + lane] = s_fin[lane];
             if (lane == 0) update_state_inplace(p, b, ch, s_c, s_o, s_u, s_fin, pblk == duty_c);
         }
         pend = false;
@@ -2323,16 +1861,12 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
     // timing probe: per-channel launch span in row 0, words 20 + 3 ch .. (block 0)
     const unsigned long long t_start = kProbe ? wall_clock64() : 0ull;
     for (int s = 0; s < nsteps; s++) {
-        s_now = s;
         const StepDesc& D = s_d[cur];
         const int bad = D.bad ? D.bad : D.bad_tap;
         const bool stop = !D.phaseC && D.Index + 1 > n1_target;  // 1-ms run of this channel done
-        // (a code rate beyond Fs/M breaks the one-boundary lane; above 3 taps one beyond the
-        // capture queue's checked rate would overflow the queue)
-        if (bad || stop || D.d * M >= 1.0 || (GNSS_QCAP && NT > kQcapMax && D.d > tk.qcap_dmax)) {
-            const bool had = pend;
+        // (a code rate beyond Fs/M breaks the one-boundary lane)
+        if (bad || stop || D.d * M >= 1.0) {
             if (pend) flush();
-            if (had) defer_final(s - 1);
             if (io && tid == 64) desc_rem(tk, &s_d[cur]);  // (complete for a step-kernel follow-up)
             __syncthreads();
             if (io) {  // leave the state and this (unused) descriptor for the host / next launch
@@ -2396,42 +1930,9 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
                 if (srow && tid == 0) srow[1] = wall_clock64();
                 if (brow && tid == 0) brow[40 + 256 + vb] = wall_clock64();
                 // block sum in a fixed order, published as granules
-                if constexpr (!kDefer) {
-                    const double bsum = block_partial<NT, HT>(s_mem, oI, oQ, tid);
-                    if (tid < NV * 4 && (tid & 3) == 0)
-                        publish16(pg, ((s & 1) * kMaxBpcRun + vb) * NV + (tid >> 2), bsum, tag0 + s + 1);
-                } else {
-                    // E / P / L first (region A), then the other taps (region B, slot s mod 4),
-                    // reduced while the exchange is in flight
-                    const double ba = block_pass<NT, HT>(s_mem, oI, oQ, tid, (unsigned)dfi(*(const int*)&s_df.selA));
-                    const int NA = NA_();
-                    if (tid < NA * 4 && (tid & 3) == 0)
-                        publish16(pg, ((s & 1) * kMaxBpcRun + vb) * NA + (tid >> 2), ba, tag0 + s + 1);
-                    if (kWave1 && dob) {
-                        // the other taps' lane values to LDS ([value][T], value = 2 rank + I/Q);
-                        // one wave reduces them during the sweep (defer_reduce)
-                        double* stg = s_mem + kPwD;
-                        const unsigned sb = (unsigned)dfi(*(const int*)&s_df.selB);
-#pragma unroll
-                        for (int s2 = 0; s2 < NT; s2++)
-                            if ((sb >> s2) & 1u) {
-                                const int r = __builtin_popcount(sb & ((1u << s2) - 1u));
-                                stg[(2 * r) * T + tid] = oI[s2];
-                                stg[(2 * r + 1) * T + tid] = oQ[s2];
-                            }
-                        lds_barrier();
-                    } else if (dob) {
-                        const int hb = dfi(s_df.hb), nB = dfi(s_df.nBv) / 2;
-                        for (int ps = 1; (ps - 1) * hb < nB; ps++) {
-                            const unsigned sel = sel_pass(ps);
-                            const double bb = block_pass<NT, HT>(s_mem, oI, oQ, tid, sel);
-                            if (tid < 2 * __builtin_popcount(sel) * 4 && (tid & 3) == 0)
-                                publish16(pg, gran_region_b(NT) + (s & 3) * gran_slot_b(NT) +
-                                                  (2 * (ps - 1) * hb + (tid >> 2)) * bpc + vb,
-                                          bb, tag0 + s + 1);
-                        }
-                    }
-                }
+                const double bsum = block_partial<NT, HT>(s_mem, oI, oQ, tid);
+                if (tid < NV * 4 && (tid & 3) == 0)
+                    publish16(pg, ((s & 1) * kMaxBpcRun + vb) * NV + (tid >> 2), bsum, tag0 + s + 1);
                 if (srow && tid == 0) srow[2] = wall_clock64();
                 if (kProbe && b.stamps && ch == 0 && tid == 0) {  // latest partial of the channel (all blocks)
                     unsigned long long* r = b.stamps + (size_t)(s % kStampSlots) * kStampRow;
@@ -2444,8 +1945,7 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
         // the step's remPhase / remSample (role 2 of the descriptor, off the tail: the
         // next tail reads them after the sweep's closing barrier)
         // (by wave 2, a poller, so that wave 1's flush of the previous step starts at once)
-        if (wv == (io ? GNSS_IO_DR_WAVE : 2) && lane == 0) desc_rem(tk, &s_d[cur]);
-        const bool bsw = kDefer && pend && own_n_() > 0;  // the previous step's owned B values are due
+        if (wv == 2 && lane == 0) desc_rem(tk, &s_d[cur]);
         if (pend) {
             if (srow && tid == 64) srow[16] = wall_clock64();
             if (brow && tid == 64) brow[40 + 1024 + blk] = wall_clock64();  // (probe: every block's flush)
@@ -2459,30 +1959,11 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
         {
             // (the part-1 and part-2 blocks: waves 0, 2, 3 poll while wave 1 writes the record;
             // the other blocks' wave 1 flush is short and it joins the polling after it)
-            int pid = GNSS_SWEEP_IO_ALL || !dsw ? tid : (wv == 1 ? -1 : tid - (wv > 1 ? 64 : 0));
-            int np = GNSS_SWEEP_IO_ALL || !dsw ? 4 * 64 : 3 * 64;
-            if (kWave1 && dob) {
-                // the B wave (wave 1, or wave 3 in the part-1 block, whose wave 1 writes the
-                // record) reduces the other taps and publishes them; the rest poll
-                const int bw = dsw ? 3 : 1;
-                if (wv == bw) defer_reduce(s);
-                // pollers: waves 0, 2, 3 (ranks 0, 1, 2); in the part-1 block waves 0, 2
-                const int rank = wv == 0 ? 0 : wv - 1;
-                pid = (wv == bw || wv == 1) ? -1 : rank * 64 + lane;
-                np = dsw ? 2 * 64 : 3 * 64;
-            }
-            if constexpr (!kDefer) {
-                if (!sweep16<(NT > 3 ? GNSS_SWEEP_BATCH : 1)>(pg, bpc * NV, tag0 + s + 1, pw, pid, np, b.run_err,
-                                                               (s & 1) * kMaxBpcRun * NV))
-                    return;
-            } else {
-                // this step's E / P / L, and the owned B values of the previous step (long published)
-                const int NA = NA_();
-                if (!sweep16x2(pg, bpc * NA, (s & 1) * kMaxBpcRun * NA, tag0 + s + 1, pw, bsw ? own_n_() * bpc : 0,
-                               gran_region_b(NT) + ((s - 1) & 3) * gran_slot_b(NT) + dfi(s_df.own_lo) * bpc, tag0 + s,
-                               pw + 2 * bpc * NA, pid, np, b.run_err))
-                    return;
-            }
+            const int pid = !dsw ? tid : (wv == 1 ? -1 : tid - (wv > 1 ? 64 : 0));
+            const int np = !dsw ? 4 * 64 : 3 * 64;
+            if (!sweep16<(NT > 3 ? kSweepBatch : 1)>(pg, bpc * NV, tag0 + s + 1, pw, pid, np, b.run_err,
+                                                      (s & 1) * kMaxBpcRun * NV))
+                return;
         }
         if (srow && tid == 0) srow[3] = wall_clock64();
         if (brow && tid == 0) brow[40 + 512 + blk] = wall_clock64();  // (probe: this block's all-in)
@@ -2495,13 +1976,12 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
                 prefetch_raw<SUB>(iq, ((A + n) >> 3) + ((int64_t)blk * T + h * 64 + lane) * SUB, gmax, s_raw,
                                   h * 64 + lane);
         }
-        if (tid < CL * NA_()) {  // (above 3 taps: the E / P / L values, at their value index)
-            const int NA = NA_();
-            const double a = channel_sum_l<CL>(bpc, tid, [&](int k, int v) {
-                const unsigned lo = pw[(k * NA + v) * 2], hi = pw[(k * NA + v) * 2 + 1];
+        if (tid < CL * NV) {
+            const double a = channel_sum<NV>(bpc, tid, [&](int k, int v) {
+                const unsigned lo = pw[(k * NV + v) * 2], hi = pw[(k * NV + v) * 2 + 1];
                 return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
             });
-            const int vi = kDefer ? s_df.vmap[tid / CL] : tid / CL;
+            const int vi = tid / CL;
             if constexpr (GNSS_CORR_PROBE != 0)  // (probe builds: E = P = L = 1, a steady loop)
                 if (tid % CL == 0) s_fin[vi] = (vi & 1) ? 0.0 * a : 1.0 + 0.0 * a;
             if constexpr (GNSS_CORR_PROBE == 0)
@@ -2565,9 +2045,6 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
                 s_o = o;
                 s_u = u;
             }
-            // (idle otherwise: the previous step's owned B values, swept beside this step's
-            // E / P / L, summed and written)
-            if (bsw) defer_write(pw + 2 * bpc * NA_());
         } else {  // wave 2: the next step's scalars and checks, then its IF has landed
             prepare_desc_i(tk, nx, o.pdi, o.phaseC, 3, lane, &s_d[cur ^ 1], s_taps, nullptr, s_post, true);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2583,9 +2060,7 @@ __global__ __launch_bounds__(kTrkThreads) __attribute__((amdgpu_waves_per_eu(NT 
         b.stamps[21 + 3 * ch] = wall_clock64();
         b.stamps[22 + 3 * ch] = (unsigned long long)nsteps;
     }
-    const bool had = pend;
     if (pend) flush();
-    if (had) defer_final(nsteps - 1);
     if (io && tid == 64) desc_rem(tk, &s_d[cur]);  // (complete for a step-kernel follow-up)
     __syncthreads();
     if (io) {  // the state and the next step's descriptor for the next launch
@@ -2708,11 +2183,11 @@ hipError_t launch_track_step(const TrkParams& p, const TrkBuffers& b, const TrkD
                              hipStream_t s)
 {
     dim3 grid(p.nch * bpc), block(kTrkThreads);
-    const bool regc = lane_regcap(p, sub);
+    const bool regc = kRegcBuilt && lane_regcap(p, sub);
 #define GNSS_STEP(NT_, SUB_, DIV_, FMT_)                                                       \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && p.fmt == FMT_) {        \
         if (NT_ <= 3 && regc)                                                                  \
-            hipLaunchKernelGGL((track_step_kernel<NT_, SUB_, DIV_, FMT_, NT_ <= 3>), grid, block, 0, s, d.p, d.b, \
+            hipLaunchKernelGGL((track_step_kernel<NT_, SUB_, DIV_, FMT_, NT_ <= 3 && kRegcBuilt>), grid, block, 0, s, d.p, d.b, \
                                bpc);                                                           \
         else                                                                                   \
             hipLaunchKernelGGL((track_step_kernel<NT_, SUB_, DIV_, FMT_>), grid, block, 0, s, d.p, d.b, bpc); \
@@ -2735,11 +2210,11 @@ hipError_t launch_track_run(const TrkParams& p, const TrkBuffers& b, const TrkDe
 {
     if (vpb < 1 || bpc < 1) return hipErrorInvalidValue;
     dim3 grid(p.nch * ((bpc + vpb - 1) / vpb)), block(kTrkThreads);
-    const bool regc = lane_regcap(p, sub);
+    const bool regc = kRegcBuilt && lane_regcap(p, sub);
 #define GNSS_RUN(NT_, SUB_, DIV_)                                                              \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && vpb == 1) {            \
         if (NT_ <= 3 && regc)                                                                  \
-            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, false, NT_ <= 3>), grid, block, 0, s, d.p, d.b, \
+            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, false, NT_ <= 3 && kRegcBuilt>), grid, block, 0, s, d.p, d.b, \
                                bpc, vpb, nsteps, tag0);                                        \
         else                                                                                   \
             hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, false>), grid, block, 0, s, d.p, d.b, bpc, \
@@ -2749,7 +2224,7 @@ hipError_t launch_track_run(const TrkParams& p, const TrkBuffers& b, const TrkDe
 #define GNSS_RUNV(NT_, SUB_, DIV_)                                                             \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && vpb > 1) {             \
         if (NT_ <= 3 && regc)                                                                  \
-            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, true, NT_ <= 3>), grid, block, 0, s, d.p, d.b, \
+            hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, true, NT_ <= 3 && kRegcBuilt>), grid, block, 0, s, d.p, d.b, \
                                bpc, vpb, nsteps, tag0);                                        \
         else                                                                                   \
             hipLaunchKernelGGL((track_run_kernel<NT_, SUB_, DIV_, true>), grid, block, 0, s, d.p, d.b, bpc, \
@@ -2768,11 +2243,11 @@ hipError_t launch_track_run(const TrkParams& p, const TrkBuffers& b, const TrkDe
 int track_run_blocks_per_cu(const TrkParams& p, int sub, bool vb)
 {
     int nb = 0;
-    const bool regc = lane_regcap(p, sub);
+    const bool regc = kRegcBuilt && lane_regcap(p, sub);
 #define GNSS_OCC(NT_, SUB_, DIV_, VB_)                                                         \
     if (p.ntaps == NT_ && sub == SUB_ && (p.exact_div != 0) == DIV_ && vb == VB_) {            \
         const void* fn = NT_ <= 3 && regc                                                      \
-                             ? reinterpret_cast<const void*>(track_run_kernel<NT_, SUB_, DIV_, VB_, NT_ <= 3>) \
+                             ? reinterpret_cast<const void*>(track_run_kernel<NT_, SUB_, DIV_, VB_, NT_ <= 3 && kRegcBuilt>) \
                              : reinterpret_cast<const void*>(track_run_kernel<NT_, SUB_, DIV_, VB_>); \
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kTrkThreads, 0) != hipSuccess) \
             nb = 0;                                                                            \

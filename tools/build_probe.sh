@@ -3,7 +3,7 @@
 # the full correlator) and GNSS_PROBE_BUILD=1 (the api_*.cpp host files read the GNSS_STAMPS /
 # GNSS_PROBE / GNSS_HOSTPROF / GNSS_FORCE_SUB10 environment hooks). Load one with
 # GNSS_LIB=<path>. Never used by the product, the tests or bench.py. EXTRA_FLAGS adds
-# compiler flags (e.g. -DGNSS_XCHG_LD_POL=17: the exchange's poll cache policy).
+# compiler flags.
 set -e
 cd "$(dirname "$0")/../assignment-for-aae6102_gnss-sdr_amd/csrc"
 make -s

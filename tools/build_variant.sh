@@ -1,7 +1,10 @@
-# Product-flag variants of the library for A/B runs: `[SRC=vt] bash tools/build_variant.sh NAME -DKNOB=v ...`
+# One kernel file rebuilt with extra flags for a measurement: `[SRC=vt] bash tools/build_variant.sh NAME FLAG ...`
 # compiles track.hip (or $SRC.hip) with the extra flags, links it with the product's other objects
 # (../build/*.o, `make` first) into tools/probe_lib/libgnss_NAME.so. Load with GNSS_LIB=<path>
-# (tools/gpu.sh ab). Never used by the product, the tests or bench.py.
+# (tools/gpu.sh ab). The kernels keep no A/B knobs: what is left to pass are the probe macros
+# (-DGNSS_CORR_PROBE=n for track.hip; SRC=vt -DGNSS_VT_PROBE=n for vt.hip; PROBE=1 adds the host's
+# hooks) and compiler options. An experiment's own variant is a source change on a branch,
+# built with tools/build_commit_lib.sh. Never used by the product, the tests or bench.py.
 set -e
 cd "$(dirname "$0")/../assignment-for-aae6102_gnss-sdr_amd/csrc"
 make -s

@@ -165,7 +165,7 @@ for step in "$@"; do
         TRK_HASH=1 TRK_PROFILE=1 TRK_ITERS=2 timeout -k 10 150 python3 tools/track_only.py 1000 90000 11 $n > gpurun_out/c5geom_$n.log 2>&1 \
           && echo "c5geom nch=$n: $(grep -E 'track10|sha256' gpurun_out/c5geom_$n.log | tail -2 | tr '\n' ' ')" || { tail -5 gpurun_out/c5geom_$n.log; exit 1; }
       done ;;
-    xstamps)  # per-block stamps + SQ counters of probe-build variants (AB="pspread pxl"): tools/stamps_blocks.py
+    xstamps)  # per-block stamps + SQ counters of probe-build variants (AB="name ..."): tools/stamps_blocks.py
       for v in $AB; do
         L=$R/tools/probe_lib/libgnss_$v.so
         GNSS_LIB=$L GNSS_STAMPS=gpurun_out/xst_$v.bin TRK_ITERS=1 timeout -k 10 120 python3 tools/track_only.py 1000 2000 > gpurun_out/xst_$v.log 2>&1 || { tail -5 gpurun_out/xst_$v.log; exit 1; }
@@ -177,14 +177,6 @@ for step in "$@"; do
         python3 tools/pmc_sq.py gpurun_out/xsq_$v.json gpurun_out/xsq1_$v gpurun_out/xsq2_$v -- "track_run_kernel<3, 3, false, false>" > /dev/null || exit 1
         python3 -c "import json; d=json.load(open('gpurun_out/xsq_$v.json')); k=[x for x in d if not x.startswith('_')][0]; print('   SQ', {c: round(w['median_per_dispatch']) for c, w in d[k].items() if isinstance(w, dict) and 'median_per_dispatch' in w})" | cut -c1-1200
         rm -f gpurun_out/xsq*_$v/**/*kernel_trace.csv
-      done ;;
-    acqpair)  # config-2 fp64 correlation by ACQ_PIPE:front (GNSS_PAIR_FRONT, probe library PAIRLIB):
-              # PAIRS="2:60 3:100 3:60 3:40" -> corr_ms of the three calls and a digest of the decisions
-      for v in ${PAIRS:-2:60 3:100 3:60 3:40}; do
-        pp=${v%%:*}; fr=${v##*:}
-        GNSS_LIB=$R/tools/probe_lib/libgnss_${PAIRLIB:-pair}.so ACQ_PIPE=$pp GNSS_PAIR_FRONT=$fr timeout -k 10 200 python3 tools/acq_only.py > gpurun_out/acqpair_${pp}_$fr.txt 2>&1 \
-          && echo "acqpair pipe=$pp front=$fr: corr_ms $(grep -o "'acq_corr_ms': [0-9.]*" gpurun_out/acqpair_${pp}_$fr.txt | cut -d' ' -f2 | tr '\n' ' ') acq_ms $(grep -o "'acq_ms': [0-9.]*" gpurun_out/acqpair_${pp}_$fr.txt | cut -d' ' -f2 | tr '\n' ' ') $(grep -E '^(fbin|snr|sv)' gpurun_out/acqpair_${pp}_$fr.txt | md5sum | cut -c1-8)" \
-          || { tail -5 gpurun_out/acqpair_${pp}_$fr.txt; exit 1; }
       done ;;
     acqlib)  # config-2 acquisition (tools/acq_only.py, fp64) under each library of ACQLIBS (tools/probe_lib/libgnss_<name>.so,
              # "prod" = the product): correlation ms of the three calls and a digest of the decisions

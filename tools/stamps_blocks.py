@@ -64,9 +64,3 @@ if m.any():
           + f"; others median {np.median(fd):.2f}")
     print("  flush start after the earliest step start: " + ", ".join(
         f"blk {b} {np.median(fs[:, b]):+.2f}" for b in top))
-# (GNSS_FLUSH_PROBE & 2 builds) block 0's record part cold, then the whole record again warm
-f0, f1, f2 = a[:, 2000], a[:, 2001], a[:, 2002]
-m = (f0 > 0) & (f1 > 0) & (f2 > 0)
-if m.any():
-    print(f"  blk0 record: first (cold) {np.median((f1 - f0)[m]) * us:.2f} us, again (warm, all fields) "
-          f"{np.median((f2 - f1)[m]) * us:.2f} us")
