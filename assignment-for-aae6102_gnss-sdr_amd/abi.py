@@ -266,6 +266,28 @@ class GnssAcfFitOut(C.Structure):
 
 ADDED_STRUCTS.update({"gnss_acf_fit_cfg": "GnssAcfFitCfg", "gnss_acf_fit_out": "GnssAcfFitOut"})
 
+# The k-NN classifier over the feature windows (gnss_knn_standardize / gnss_knn_classify; additive
+# within ABI v13): its limits and the two flags
+KNN_MAX_D, KNN_MAX_K, KNN_MAX_CLASS, KNN_MAX_M = 16, 32, 8, 1 << 24
+KNN_HOST = 1          # gnss_knn_cfg.flags
+KNN_MODEL_DEVICE = 1  # gnss_knn_model.flags
+
+
+class GnssKnnCfg(C.Structure):
+    _fields_ = [("k", C.c_int32), ("flags", C.c_int32)]
+
+
+class GnssKnnModel(C.Structure):
+    _fields_ = [("M", C.c_int64), ("D", C.c_int32), ("n_class", C.c_int32), ("mu", C.c_void_p), ("inv", C.c_void_p),
+                ("z", C.c_void_p), ("label", C.c_void_p), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GnssKnnOut(C.Structure):
+    _fields_ = [("label", C.c_void_p), ("votes", C.c_void_p), ("nn_index", C.c_void_p), ("nn_d2", C.c_void_p)]
+
+
+ADDED_STRUCTS.update({"gnss_knn_cfg": "GnssKnnCfg", "gnss_knn_model": "GnssKnnModel", "gnss_knn_out": "GnssKnnOut"})
+
 
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
@@ -402,6 +424,10 @@ PROTOTYPES = {
                                C.POINTER(GnssAcfFitOut)]),
     "gnss_acf_fit_window": (C.c_int, [C.POINTER(GnssAcfFitCfg), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(GnssAcfFitOut)]),
+    # the k-NN classifier over the feature windows (additive within ABI v13: detected by symbol)
+    "gnss_knn_standardize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gnss_knn_classify": (C.c_int, [C.c_void_p, C.POINTER(GnssKnnCfg), C.POINTER(GnssKnnModel), C.c_void_p,
+                                    C.c_int64, C.POINTER(GnssKnnOut)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

@@ -1470,3 +1470,161 @@ def scene_labels(scene, TckResults_multiCorr, prnList, *, ind_start: int = 1, nu
                 lab[m] = 1
         out.append(lab)
     return out
+
+
+# ---------------------------------------------------------------------------
+# the classifier data_labeled is the training set of: k nearest neighbours over the feature windows
+# ---------------------------------------------------------------------------
+# feature_table's column names -> (which namespace, its field)
+_KNN_COLUMNS = {"F1": ("features", "F1"), "F2": ("features", "F2"), "F3": ("features", "varDelay"),
+                "F4": ("features", "meanCodeDisc"), "F5": ("features", "varCodeDisc"),
+                "numMLC": ("features", "numMLC"), "fftFreq": ("features", "fftFreq"), "fftMag": ("features", "fftMag"),
+                "bias": ("fit", "bias"), "ratio": ("fit", "ratio")}
+
+
+def feature_table(features, fit=None, columns=None):
+    """The [Q][D] table of an acf_features namespace and, if given, the acf_fit namespace of the
+    same windows: one row per window, all channels concatenated in prnList order (which lines up
+    with np.concatenate(scene_labels(...))). Default columns: F1, F2, F3 (varDelay), F4
+    (meanCodeDisc), F5 (varCodeDisc), then numMLC, fftFreq, fftMag when the namespace is extended,
+    then bias, ratio when `fit` is given. columns= selects by these names (any other per-window
+    field of the two namespaces by its own name, e.g. "meanMax" or "e"); a name the inputs do not
+    carry is a ValueError."""
+    if columns is None:
+        columns = ["F1", "F2", "F3", "F4", "F5"]
+        if hasattr(features, "numMLC"):
+            columns += ["numMLC", "fftFreq", "fftMag"]
+        if fit is not None:
+            columns += ["bias", "ratio"]
+    src = {"features": features, "fit": fit}
+    windows = [int(w) for w in features.windows]
+    cols = []
+    for name in columns:
+        where, field = _KNN_COLUMNS.get(name, (None, name))
+        holders = [src[where]] if where else [features, fit]
+        per = next((getattr(h, field) for h in holders if h is not None and isinstance(getattr(h, field, None), list)),
+                   None)
+        if per is None or len(per) != len(windows) or any(np.shape(a) != (w,) for a, w in zip(per, windows)):
+            raise ValueError(f"feature_table: the inputs carry no per-window column {name!r}")
+        cols.append(np.concatenate([np.asarray(a, dtype=np.float64) for a in per]) if per else np.zeros(0))
+    return np.column_stack(cols).reshape(sum(windows), len(cols)) if cols else np.zeros((sum(windows), 0))
+
+
+def _knn_status(lib, h, st):
+    if st != abi.OK:
+        raise abi.GnssError(st, (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode())
+
+
+class KnnModel:
+    """A trained k-NN model (knn_train): mu, inv [D], the standardised rows z [M][D], label [M],
+    n_class, .dropped (the training rows left out for a non-finite value) and, trained with a
+    context, z and label resident in its HBM until .free()."""
+
+    def __init__(self, mu, inv, z, label, n_class, dropped, ctx=None):
+        self.mu, self.inv, self.z, self.label = mu, inv, z, label
+        self.n_class, self.dropped, self.ctx = int(n_class), int(dropped), None
+        self.dev_z = self.dev_label = None
+        if ctx is not None:
+            lib = ctx.lib
+            try:
+                for name, a in (("dev_z", z), ("dev_label", label)):
+                    p = C.c_void_p()
+                    ctx.check(lib.gnss_dev_alloc(ctx.h, C.c_uint64(a.nbytes), C.byref(p)))
+                    setattr(self, name, p)
+                    ctx.check(lib.gnss_dev_upload(ctx.h, p, a.ctypes.data_as(C.c_void_p), C.c_uint64(a.nbytes)))
+            except Exception:
+                self.ctx = ctx
+                self.free()
+                raise
+            self.ctx = ctx
+
+    M = property(lambda self: self.z.shape[0])
+    D = property(lambda self: self.z.shape[1])
+    resident = property(lambda self: self.ctx is not None and self.dev_z is not None and self.dev_label is not None)
+
+    def free(self):
+        """Releases the resident copies (the host arrays stay: the model still classifies)."""
+        if self.ctx is not None and getattr(self.ctx, "h", None):
+            for p in (self.dev_z, self.dev_label):
+                if p:
+                    self.ctx.lib.gnss_dev_free(self.ctx.h, p)
+        self.dev_z = self.dev_label = self.ctx = None
+
+    def c_model(self, device: bool):
+        m = abi.GnssKnnModel()
+        m.M, m.D, m.n_class = self.M, self.D, self.n_class
+        m.mu, m.inv = self.mu.ctypes.data, self.inv.ctypes.data
+        if device:
+            m.z, m.label, m.flags = self.dev_z.value, self.dev_label.value, abi.KNN_MODEL_DEVICE
+        else:
+            m.z, m.label = self.z.ctypes.data, self.label.ctypes.data
+        return m
+
+
+def knn_train(X, y, n_class: int = 3, ctx: Context | None = None) -> KnnModel:
+    """A k-NN model of the table X [M][D] (feature_table) and its labels y [M] in 0..n_class-1
+    (np.concatenate(scene_labels(...))). Rows with a non-finite value are dropped first and
+    counted in .dropped; the columns are standardised by gnss_knn_standardize (a constant column
+    drops out of every distance). With ctx the standardised rows and the labels are uploaded once
+    and stay resident for knn_classify until .free(). Host work only otherwise."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    y = np.asarray(y)
+    if X.ndim != 2 or y.shape != (X.shape[0],):
+        raise ValueError("knn_train: X [M][D] and y [M]")
+    keep = np.all(np.isfinite(X), axis=1)
+    dropped = int(np.sum(~keep))
+    X, label = np.ascontiguousarray(X[keep]), np.ascontiguousarray(y[keep], dtype=np.int32)
+    M, D = X.shape
+    if M and not np.array_equal(label, y[keep]):
+        raise ValueError("knn_train: y holds a value that is no 32-bit integer")
+    if M and (label.min() < 0 or label.max() >= int(n_class)):
+        raise ValueError(f"knn_train: a label outside 0..{int(n_class) - 1}")
+    mu, inv, z = np.zeros(max(D, 1)), np.zeros(max(D, 1)), np.zeros((M, D))
+    lib = abi.load()
+    _knn_status(lib, None, lib.gnss_knn_standardize(X.ctypes.data, M, D, mu.ctypes.data, inv.ctypes.data,
+                                                    z.ctypes.data))
+    return KnnModel(mu[:D].copy(), inv[:D].copy(), z, label, n_class, dropped, ctx)
+
+
+def knn_classify(model: KnnModel, X, k: int = 5, ctx: Context | None = None, want_neighbours: bool = False):
+    """The rows of X [Q][D] labelled by the vote of their k nearest training rows
+    (gnss_knn_classify): a namespace of label [Q] (-1 for a row with a non-finite value),
+    votes [Q][n_class] and, with want_neighbours, nn_index [Q][k] (rows of the model's table after
+    the dropped ones were taken out, nearest first) and nn_d2 [Q][k] (squared distances in
+    standardised units). A resident model runs on its context's GPU; with ctx a host model is
+    uploaded for the call; with neither the host path runs (no GPU needed). The three give the
+    same bits."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != model.D:
+        raise ValueError(f"knn_classify: X [Q][{model.D}]")
+    if model.resident and ctx is not None and ctx is not model.ctx:
+        raise ValueError("knn_classify: the model is resident on another context")
+    run_ctx = model.ctx if model.resident else ctx
+    Q, k = X.shape[0], int(k)
+    cfg = abi.GnssKnnCfg()
+    cfg.k = k
+    cm = model.c_model(model.resident)
+    kk = max(k, 1)
+    res = SimpleNamespace(label=np.full(Q, -1, dtype=np.int32), votes=np.zeros((Q, model.n_class), dtype=np.int32))
+    out = abi.GnssKnnOut()
+    out.label, out.votes = res.label.ctypes.data, res.votes.ctypes.data
+    if want_neighbours:
+        res.nn_index, res.nn_d2 = np.full((Q, kk), -1, dtype=np.int32), np.full((Q, kk), np.nan)
+        out.nn_index, out.nn_d2 = res.nn_index.ctypes.data, res.nn_d2.ctypes.data
+    lib = abi.load()
+    h = run_ctx.h if run_ctx is not None else None
+    _knn_status(lib, h, lib.gnss_knn_classify(h, C.byref(cfg), C.byref(cm), X.ctypes.data, Q, C.byref(out)))
+    return res
+
+
+def confusion(y_true, y_pred, n_class: int = 3) -> np.ndarray:
+    """[n_class][n_class + 1] counts: row = the true class, column = the predicted one, the last
+    column the rows that got no label (-1)."""
+    yt, yp = np.asarray(y_true).astype(np.int64).ravel(), np.asarray(y_pred).astype(np.int64).ravel()
+    if yt.shape != yp.shape:
+        raise ValueError("confusion: y_true and y_pred differ in length")
+    if yt.size and (yt.min() < 0 or yt.max() >= n_class or yp.min() < -1 or yp.max() >= n_class):
+        raise ValueError("confusion: a class outside 0..n_class-1 (or a prediction below -1)")
+    m = np.zeros((n_class, n_class + 1), dtype=np.int64)
+    np.add.at(m, (yt, np.where(yp < 0, n_class, yp)), 1)
+    return m

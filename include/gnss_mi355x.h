@@ -1037,6 +1037,69 @@ int gnss_acf_fit(gnss_ctx *ctx, const gnss_acf_fit_cfg *cfg, const gnss_track_ou
 int gnss_acf_fit_window(const gnss_acf_fit_cfg *cfg, const double *zI, const double *zQ,
                         gnss_acf_fit_out *out);
 
+/* ---- k-NN classifier over the feature windows (additive within ABI v13; detected by symbol) --
+ * ACF/CalculateFeatures.m names its table data_labeled: a training set for a classifier that
+ * says, per 100-ms window, line of sight / multipath / no direct signal (0 / 1 / 2, the labels of
+ * a synthetic scene). A brute-force k-nearest-neighbour vote on standardised columns; it goes
+ * beyond the reference, which stops at the table. All arithmetic fp64, every operation rounded on
+ * its own, every sum left to right from its first term (csrc/knn.h is the one source for host
+ * and device).
+ *   - Standardisation of x[M][D]: mu[j] = (sum_t x[t][j]) / M, var[j] = (sum_t (x[t][j] - mu[j]) *
+ *     (x[t][j] - mu[j])) / M, sd[j] = sqrt(var[j]), inv[j] = 1 / sd[j] or 0 when sd[j] == 0 (a
+ *     constant column drops out of every distance), z[t][j] = (x[t][j] - mu[j]) * inv[j].
+ *   - Query q[D]: zq[j] = (q[j] - mu[j]) * inv[j], d2(t) = sum_j (zq[j] - z[t][j]) * (zq[j] -
+ *     z[t][j]), j ascending. A query with a non-finite q[j] (the raw value: also on a column
+ *     with inv[j] = 0) gets label -1, all votes 0, every neighbour index -1 and d2 NaN.
+ *   - Neighbours: the k smallest training rows under the total order (d2, t): the smaller d2
+ *     first, on equal d2 the smaller row; +inf is an ordinary value and a NaN d2 (a finite query
+ *     so far out that q[j] - mu[j] overflows on a constant column) comes after it, stored as the
+ *     quiet NaN 0x7ff8000000000000. Returned ascending in that order.
+ *   - votes[c]: the neighbours of class c; label: the class with the most votes, among tied
+ *     classes the one that owns the nearest neighbour.                                        */
+#define GNSS_KNN_HOST         1  /* gnss_knn_cfg.flags: the host path also with a context      */
+#define GNSS_KNN_MODEL_DEVICE 1  /* gnss_knn_model.flags: z and label are DEVICE pointers of the
+                                    context's device (gnss_dev_alloc / gnss_dev_upload)        */
+typedef struct gnss_knn_cfg {
+    int32_t k;                /* neighbours, 1..32 and <= M                                    */
+    int32_t flags;            /* GNSS_KNN_HOST or 0                                            */
+} gnss_knn_cfg;
+
+typedef struct gnss_knn_model {
+    int64_t        M;         /* training rows, 1..2^24                                        */
+    int32_t        D;         /* columns, 1..16                                                */
+    int32_t        n_class;   /* classes, 1..8                                                 */
+    const double  *mu, *inv;  /* [D], host                                                     */
+    const double  *z;         /* [M][D] standardised rows                                      */
+    const int32_t *label;     /* [M], each in 0..n_class-1                                     */
+    int32_t        flags;     /* GNSS_KNN_MODEL_DEVICE or 0                                    */
+    int32_t        reserved;
+} gnss_knn_model;
+
+/* Caller-allocated host arrays. nn_index and nn_d2 are optional (NULL: not wanted). */
+typedef struct gnss_knn_out {
+    int32_t *label;           /* [Q]                                                           */
+    int32_t *votes;           /* [Q][n_class]                                                  */
+    int32_t *nn_index;        /* [Q][k] training rows, nearest first; may be NULL              */
+    double  *nn_d2;           /* [Q][k]; may be NULL                                           */
+} gnss_knn_out;
+
+/* mu[D], inv[D] and z[M][D] of the training table x[M][D] (above). Host only. GNSS_EARG for a
+ * null array, M outside 1..2^24, D outside 1..16, a non-finite x or a non-finite mu, sd or inv. */
+int gnss_knn_standardize(const double *x, int64_t M, int32_t D, double *mu, double *inv, double *z);
+
+/* Q query rows q[Q][D] (host, raw) against the model. ctx == NULL or GNSS_KNN_HOST: on the host,
+ * the queries dealt over up to 16 threads. Otherwise on the GPU (csrc/knn.hip): q and the outputs
+ * stay host arrays; model->z and model->label are host arrays that the call uploads, or with
+ * GNSS_KNN_MODEL_DEVICE device arrays that stay where they are (a caller that classifies many
+ * record sets uploads the model once). Both paths give the same bits in every output. Checked on
+ * the host before any launch, GNSS_EARG otherwise and the context usable after: D in 1..16, k in
+ * 1..32 and <= M, n_class in 1..8, every training label in 0..n_class-1, M in 1..2^24, Q >= 0
+ * (Q == 0: GNSS_OK, nothing written), no null array that is not optional, no unknown flag, a
+ * device model only with a context and the device path, and no context of gnss_ctx_create_multi
+ * on the device path. */
+int gnss_knn_classify(gnss_ctx *ctx, const gnss_knn_cfg *cfg, const gnss_knn_model *model,
+                      const double *q, int64_t Q, gnss_knn_out *out);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
