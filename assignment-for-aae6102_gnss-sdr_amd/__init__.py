@@ -15,11 +15,13 @@ from .sdr import (Context, DeviceRecord, DeviceTrackOutBuffers, StructArray, Tra
                   trackingCT_POS, trackingCT_POS_updated_multicorrelator, trackingVT_POS_updated, trackingVT_run, trackingVT_step,
                   trackingVT_POS_updated_multicorrelator, trackingVT_mc_run, trackingVT_mc_step, vt_channel,
                   NavSolCtBuffers, ct_positioning, findPosSV, trackingCT_POS_updated, acf_features, acf_fit, CalculateFeatures,
-                  scene_labels, feature_table, KnnModel, knn_train, knn_classify, confusion)
+                  scene_labels, feature_table, KnnModel, knn_train, knn_classify, confusion, replay_rows, replay_correlate,
+                  replay_coherent)
 
 __all__ = ["abi", "synth", "Context", "DeviceRecord", "DeviceTrackOutBuffers", "StructArray", "TrackOutBuffers",
            "acquisition", "ca_code", "colon", "default_context", "initParameters", "naviDecode_updated",
            "trackingCT", "trackingCT_multiCorr", "trackingCT_POS", "trackingCT_POS_updated_multicorrelator", "trackingVT_POS_updated", "trackingVT_run", "trackingVT_step",
            "trackingVT_POS_updated_multicorrelator", "trackingVT_mc_run", "trackingVT_mc_step", "vt_channel",
            "NavSolCtBuffers", "ct_positioning", "findPosSV", "trackingCT_POS_updated", "acf_features", "acf_fit",
-           "CalculateFeatures", "scene_labels", "feature_table", "KnnModel", "knn_train", "knn_classify", "confusion"]
+           "CalculateFeatures", "scene_labels", "feature_table", "KnnModel", "knn_train", "knn_classify", "confusion",
+           "replay_rows", "replay_correlate", "replay_coherent"]

@@ -288,6 +288,29 @@ class GnssKnnOut(C.Structure):
 
 ADDED_STRUCTS.update({"gnss_knn_cfg": "GnssKnnCfg", "gnss_knn_model": "GnssKnnModel", "gnss_knn_out": "GnssKnnOut"})
 
+# The replay correlator (gnss_replay_correlate; additive within ABI v13): recorded tracking rows
+# correlated again on any tap grid
+REPLAY_MAX_TAPS = 256
+
+
+class GnssReplayCfg(C.Structure):
+    _fields_ = [("n_taps", C.c_int32), ("chip_off", C.c_int32), ("tap_offsets", C.c_void_p), ("post", C.c_void_p),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GnssReplayRows(C.Structure):
+    _fields_ = [("n_chan", C.c_int32), ("reserved", C.c_int32), ("max_rows", C.c_int64), ("prn", C.c_void_p),
+                ("n_rows", C.c_void_p), ("pos_bytes", C.c_void_p), ("numSample", C.c_void_p), ("remChip", C.c_void_p),
+                ("codeFreq", C.c_void_p), ("carrFreq", C.c_void_p), ("remPhase", C.c_void_p)]
+
+
+class GnssReplayOut(C.Structure):
+    _fields_ = [("taps", C.c_void_p), ("kernel_ms", C.c_double)]
+
+
+ADDED_STRUCTS.update({"gnss_replay_cfg": "GnssReplayCfg", "gnss_replay_rows": "GnssReplayRows",
+                      "gnss_replay_out": "GnssReplayOut"})
+
 
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
@@ -428,6 +451,10 @@ PROTOTYPES = {
     "gnss_knn_standardize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gnss_knn_classify": (C.c_int, [C.c_void_p, C.POINTER(GnssKnnCfg), C.POINTER(GnssKnnModel), C.c_void_p,
                                     C.c_int64, C.POINTER(GnssKnnOut)]),
+    # the replay correlator (additive within ABI v13: detected by symbol)
+    "gnss_replay_correlate": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal),
+                                        C.POINTER(GnssReplayCfg), C.POINTER(GnssReplayRows),
+                                        C.POINTER(GnssReplayOut)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

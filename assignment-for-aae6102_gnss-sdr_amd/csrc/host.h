@@ -182,6 +182,27 @@ int stage_into(gnss_ctx* ctx, const gnss_file* f, int64_t lo, int64_t hi, int8_t
 int stage_window(gnss_ctx* ctx, const gnss_file* f, int64_t lo, int64_t hi, IfWindow& w);
 // The HIP device a device pointer belongs to (-1 if HIP does not know it).
 int pointer_device(const void* p);
+// [p, p + bytes) is device memory of `device` inside one allocation, as HIP knows it (a host
+// pointer, registered or not, is not: the kernels would read it as a device address)
+inline bool device_memory_of(const void* p, size_t bytes, int device)
+{
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != device || a.devicePointer == nullptr) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const char* lo = static_cast<const char*>(base);
+    const char* q = static_cast<const char*>(p);
+    return q >= lo && bytes <= size && (size_t)(q - lo) <= size - bytes;
+}
+
 // drops the resident copies of every member of ctx that overlap [p, p + n) (n == 0: the records
 // containing p; p == nullptr: all of them); returns how many were dropped
 int drop_resident(gnss_ctx* ctx, const void* p, uint64_t n);

@@ -18,27 +18,6 @@ namespace {
 
 constexpr int kHostBlock = 64;  // queries a host thread takes at a time
 
-// [p, p + bytes) is device memory of `device` inside one allocation, as HIP knows it (a host
-// pointer, registered or not, is not: the kernels would read it as a device address)
-bool device_memory_of(const void* p, size_t bytes, int device)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    if (a.type != hipMemoryTypeDevice || a.device != device || a.devicePointer == nullptr) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    const char* lo = static_cast<const char*>(base);
-    const char* q = static_cast<const char*>(p);
-    return q >= lo && bytes <= size && (size_t)(q - lo) <= size - bytes;
-}
-
 void host_classify(const gnss_knn_model& m, int k, const double* q, int64_t Q, gnss_knn_out* out)
 {
     const int64_t blocks = (Q + kHostBlock - 1) / kHostBlock;

@@ -1628,3 +1628,142 @@ def confusion(y_true, y_pred, n_class: int = 3) -> np.ndarray:
     m = np.zeros((n_class, n_class + 1), dtype=np.int64)
     np.add.at(m, (yt, np.where(yp < 0, n_class, yp)), 1)
     return m
+
+
+# ---------------------------------------------------------------------------
+# The replay correlator: recorded tracking rows on any tap grid (gnss_replay_correlate)
+# ---------------------------------------------------------------------------
+_REPLAY_SERIES = ("remChip", "codeFreq", "carrierFreq", "remPhase", "absoluteSample", "numSample")
+
+
+def replay_rows(records, Acquired, file, signal, loop: str = "given", rows=None):
+    """The replay table of a tracking result: per channel and row the NCO state its correlation
+    started from. Row i of a loop reads numSample(i) samples from byte absoluteSample(i-1) with
+    remChip, codeFreq, carrierFreq and remPhase as row i-1 left them; row 0 takes the loop's initial
+    state (0, codeFreqBasis, fineFreq, 0) and its seek.
+
+    `records`: the raw TrackOutBuffers (raw=True) of trackingCT_multiCorr (loop="given"),
+    trackingCT_POS_updated_multicorrelator ("mc") or trackingCT_POS ("pos"); of device-resident
+    records only those six series are downloaded. `rows`: the record rows to take, ascending
+    indices applied to every channel (None: all of each channel). Returns a namespace with the
+    table (prn, n_rows, max_rows, pos_bytes, numSample, remChip, codeFreq, carrFreq, remPhase
+    [n_chan][max_rows]), rows (the record row of each table row), and what replays the loop's own
+    correlation: taps, chip_off and post (0 / none for "given", 1 / none for "mc", 0 /
+    [0, 0.05, 0] on the E / P / L taps [0.5, 0, -0.5] for "pos")."""
+    if loop not in ("given", "mc", "pos"):
+        raise ValueError('replay_rows: loop is "given", "mc" or "pos"')
+    if not isinstance(records, TrackOutBuffers):
+        raise ValueError("replay_rows: the raw TrackOutBuffers of a tracking loop (raw=True)")
+    nch = len(Acquired.sv)
+    idx = [abi.FIELDS.index(f) for f in _REPLAY_SERIES]
+    if isinstance(records, DeviceTrackOutBuffers):
+        records.sync_producer()
+        ser = records.rec[:nch, idx, :].cpu().numpy()
+    else:
+        ser = np.asarray(records.rec)[:nch][:, idx, :]
+    lens = [int(x) for x in np.asarray(records.len)[:nch]]
+    S, skip = int(signal.Sample), int(file.skip)
+    bps = int(file.dataPrecision) * int(file.dataType)
+    sel = None if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    if sel is not None and len(sel) and (np.any(sel < 0) or np.any(np.diff(sel) <= 0)):
+        raise ValueError("replay_rows: rows are ascending record row indices")
+    per = [np.arange(n) if sel is None else sel[sel < n] for n in lens]
+    max_rows = max([len(p) for p in per] + [1])
+    t = SimpleNamespace(prn=np.array([int(p) for p in Acquired.sv], dtype=np.int32),
+                        n_rows=np.array([len(p) for p in per], dtype=np.int64), max_rows=max_rows,
+                        pos_bytes=np.zeros((nch, max_rows), dtype=np.int64),
+                        numSample=np.zeros((nch, max_rows), dtype=np.int64),
+                        remChip=np.zeros((nch, max_rows)), codeFreq=np.zeros((nch, max_rows)),
+                        carrFreq=np.zeros((nch, max_rows)), remPhase=np.zeros((nch, max_rows)),
+                        rows=per, loop=loop)
+    for c in range(nch):
+        cd = int(Acquired.codedelay[c])
+        if loop == "given":  # trackingCT_multiCorr-GIVEN.m:57
+            seek = (S - cd - 1 + skip * S) * bps
+        else:                # trackingCT_POS_updated(_multicorrelator).m:108-110
+            seek = int((S - cd + 1 + skip * signal.Fs * signal.ms) * bps)
+        # the state before each row: the initial one, then every row's record
+        start = np.empty((5, lens[c] + 1))
+        start[:, 0] = [0.0, signal.codeFreqBasis, float(Acquired.fineFreq[c]), 0.0, float(seek)]
+        start[:, 1:] = ser[c, :5, : lens[c]]
+        r = per[c]
+        k = len(r)
+        t.remChip[c, :k], t.codeFreq[c, :k] = start[0, r], start[1, r]
+        t.carrFreq[c, :k], t.remPhase[c, :k] = start[2, r], start[3, r]
+        t.pos_bytes[c, :k] = np.rint(start[4, r]).astype(np.int64)
+        t.numSample[c, :k] = np.rint(ser[c, 5, r]).astype(np.int64)
+    spacing = colon(0.6, -0.05, -0.6)
+    if loop == "given":
+        t.taps, t.chip_off, t.post = colon(-0.6, 0.05, 0.6), 0, None
+    elif loop == "mc":
+        t.taps, t.chip_off, t.post = spacing, 1, None
+    else:
+        t.taps, t.chip_off, t.post = spacing[[2, 12, 22]], 0, np.array([0.0, 0.05, 0.0])
+    return t
+
+
+def replay_correlate(file, signal, rows, taps, chip_off: int = 0, post=None, ctx: Context | None = None,
+                     device_out: bool = False):
+    """Every tap's (I, Q) sum of every row of a replay table (replay_rows, or any namespace with
+    its arrays) -> (taps_out, kernel_ms): taps_out [n_chan, 2, n_taps, max_rows] (I then Q, the
+    layout of gnss_track_out.taps; rows beyond a channel's n_rows stay 0). `taps`: up to 256
+    offsets in chips (a tap delays the replica: a ray tau chips late shows at tap -tau);
+    chip_off / post as replay_rows returns them for the loop. ctx=None runs the host path (no
+    GPU needed), a Context the kernel; device_out=True returns a torch tensor on the context's
+    device (GNSS_OUT_DEVICE) instead of a numpy array."""
+    f, k1 = to_c_file(file)
+    s = to_c_signal(signal)
+    tp = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+    cfg = abi.GnssReplayCfg()
+    cfg.n_taps, cfg.chip_off = len(tp), int(chip_off)
+    cfg.tap_offsets = tp.ctypes.data
+    if post is not None:
+        po = np.ascontiguousarray(post, dtype=np.float64).reshape(-1)
+        if len(po) != len(tp):
+            raise ValueError("replay_correlate: post has one value per tap")
+        cfg.post = po.ctypes.data
+    nch, max_rows = len(rows.prn), int(rows.max_rows)
+    keep = {"prn": np.ascontiguousarray(rows.prn, dtype=np.int32), "n_rows": np.ascontiguousarray(rows.n_rows, dtype=np.int64)}
+    for name, dt in (("pos_bytes", np.int64), ("numSample", np.int64), ("remChip", np.float64),
+                     ("codeFreq", np.float64), ("carrFreq", np.float64), ("remPhase", np.float64)):
+        a = np.ascontiguousarray(getattr(rows, name), dtype=dt)
+        if a.shape != (nch, max_rows):
+            raise ValueError(f"replay_correlate: rows.{name} is not [n_chan][max_rows]")
+        keep[name] = a
+    r = abi.GnssReplayRows()
+    r.n_chan, r.max_rows = nch, max_rows
+    for name, a in keep.items():
+        setattr(r, name, a.ctypes.data)
+    out = abi.GnssReplayOut()
+    if device_out:
+        if ctx is None:
+            raise ValueError("replay_correlate: device_out needs a Context")
+        torch = abi.require_torch()
+        res = torch.zeros((nch, 2, len(tp), max_rows), dtype=torch.float64, device=f"cuda:{ctx.device}")
+        torch.cuda.current_stream(res.device).synchronize()
+        out.taps = res.data_ptr()
+        cfg.flags = abi.OUT_DEVICE
+    else:
+        res = np.zeros((nch, 2, len(tp), max_rows))
+        out.taps = res.ctypes.data
+    lib = abi.load()
+    h = ctx.h if ctx is not None else None
+    st = lib.gnss_replay_correlate(h, C.byref(f), C.byref(s), C.byref(cfg), C.byref(r), C.byref(out))
+    if st != abi.OK:
+        msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
+        raise abi.GnssError(st, msg)
+    return res, float(out.kernel_ms)
+
+
+def replay_coherent(taps_out, prompt, rows_per_window: int):
+    """Each window's rows summed per tap with the sign of the prompt's I (the data-bit wipe of
+    acf_fit, in numpy). taps_out [n_chan, 2, n_taps, n_rows] (replay_correlate's, cut to the
+    rows wanted), prompt [n_chan, n_rows] the prompt's I of the same rows ->
+    [n_chan, 2, n_taps, n_rows // rows_per_window]."""
+    t = np.asarray(taps_out, dtype=np.float64)
+    p = np.asarray(prompt, dtype=np.float64)
+    w = int(rows_per_window)
+    nwin = t.shape[3] // w
+    sign = np.where(p[:, : nwin * w] < 0, -1.0, 1.0)
+    z = t[:, :, :, : nwin * w] * sign[:, None, None, :]
+    return z.reshape(t.shape[0], 2, t.shape[2], nwin, w).sum(axis=4)

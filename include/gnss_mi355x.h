@@ -1100,6 +1100,84 @@ int gnss_knn_standardize(const double *x, int64_t M, int32_t D, double *mu, doub
 int gnss_knn_classify(gnss_ctx *ctx, const gnss_knn_cfg *cfg, const gnss_knn_model *model,
                       const double *q, int64_t Q, gnss_knn_out *out);
 
+/* ---- replay correlator (additive within ABI v13; detected by symbol) -----------------------
+ * Recorded tracking rows correlated again on any tap grid, with no loop closed. Every 25-tap loop
+ * freezes its taps at -0.6:0.05:0.6 chip when it runs; a reflected ray later than that is outside
+ * every record. A row's correlation, though, is fixed by the NCO state the loop left after the row
+ * before it and by the row's own read: row i starts at byte absoluteSample(i-1) with
+ * remChip(i-1), codeFreq(i-1), carrierFreq(i-1), remPhase(i-1) and reads numSample(i) samples
+ * (row 0: the loop's initial state and seek). Replayed with the loop's own taps a row returns the
+ * recorded sums; with other taps it shows the correlation function wherever the caller looks.
+ * Rows are independent of each other, so the GPU path (csrc/replay.hip) has one workgroup per
+ * (row, channel, tile of 32 taps) and no hand-off between workgroups.
+ *
+ * Per row and tap s (correlate_cpx of the reference loops, trackingCT.m:96-118):
+ *   d = codeFreq / Fs; tap s's time axis is MATLAB's colon
+ *   ((0 + tap[s]) + remChip) : d : (((n-1)*d + tap[s]) + remChip), which must have exactly n
+ *   elements (else GNSS_EINDEX, the error text naming channel, row and tap); t = element k, plus
+ *   post[s] if post is given; chip CA[(ceil(t) + chip_off + 1022) mod 1023] with a true modulus, so
+ *   any finite tap works. chip_off = 0 is Code(ceil(t)+1) of trackingCT.m and
+ *   trackingCT_multiCorr-GIVEN.m, chip_off = 1 Code(ceil(t)+2) of the two _POS siblings. Inside the
+ *   reference's padded code tables this is the chip they hold; outside it is the code's PERIODIC
+ *   EXTENSION, without the data bit's flips (a tap far from the prompt crosses bit edges the
+ *   replica does not know).
+ *   Carrier: Wave(k) = 2*pi*(carrFreq*(k/Fs)) + remPhase with the reference's roundings,
+ *   I = xr*sin + xi*cos, Q = xr*cos - xi*sin, summed in fp64 in a fixed order.
+ * A tap offset delays the REPLICA, so a ray that arrives tau chips late shows at tap -tau: the
+ * delayed ray appears at negative taps (as in the 25-tap records of the GIVEN loop).
+ * Records are int8, dataType 2 (I/Q pairs) or 1 (real, xi = 0); int16 records: GNSS_EARG.
+ * A row's bits depend on that row alone: not on the other rows or channels of the call, on host or
+ * device output, on how the call was segmented (gnss_ctx_set_window), or on the run (no float
+ * atomics). The host path and the GPU path sum in different orders and agree to rounding. */
+#define GNSS_REPLAY_MAX_TAPS 256
+typedef struct gnss_replay_cfg {
+    int32_t       n_taps;       /* 1..GNSS_REPLAY_MAX_TAPS                                      */
+    int32_t       chip_off;     /* 0 or 1                                                       */
+    const double *tap_offsets;  /* [n_taps] chips, finite, |tap| <= 1023                        */
+    const double *post;         /* [n_taps] added to a tap's element before ceil (the +0.05 of
+                                   trackingCT_POS_updated.m:216), |post| <= 1023; NULL = none   */
+    int32_t       flags;        /* GNSS_OUT_DEVICE: out->taps is a DEVICE pointer, or 0         */
+    int32_t       reserved;
+} gnss_replay_cfg;
+
+/* The rows' NCO states, [n_chan][max_rows] arrays of which channel c uses rows 0..n_rows[c]-1. */
+typedef struct gnss_replay_rows {
+    int32_t        n_chan;      /* 1..GNSS_MAX_SV                                               */
+    int32_t        reserved;
+    int64_t        max_rows;
+    const int32_t *prn;         /* [n_chan] 1..51                                               */
+    const int64_t *n_rows;      /* [n_chan] 0..max_rows (0: the channel sits the call out)      */
+    const int64_t *pos_bytes;   /* the row's first file byte                                    */
+    const int64_t *numSample;   /* samples read, 1..2^22                                        */
+    const double  *remChip;     /* at the row's start                                           */
+    const double  *codeFreq;    /* > 0; (numSample-1) * codeFreq / Fs at most 2^28 chips        */
+    const double  *carrFreq;
+    const double  *remPhase;
+} gnss_replay_rows;
+
+typedef struct gnss_replay_out {
+    double *taps;       /* [n_chan][2][n_taps][max_rows], gnss_track_out.taps' layout: I then Q;
+                           rows >= n_rows[c] are left untouched                                 */
+    double  kernel_ms;  /* out: hipEvents around the kernel(s); 0 on the host path              */
+} gnss_replay_out;
+
+/* ctx == NULL: the host path (up to 16 threads, the rows dealt over them; the bits do not depend on
+ * the thread count), the record from file->data or file->path. Otherwise the GPU: the bytes
+ * [min pos_bytes, max row end) are staged into HBM (a dev_data record is read where it lies); if
+ * they exceed the context's window (gnss_ctx_set_window) the rows are processed in consecutive
+ * segments, each staging its own range (GNSS_EARG if one row index of all channels does not fit;
+ * gnss_last_timing's track_segments then holds the segment count, h2d_ms / h2d_bytes the staging).
+ * Everything is checked on the host before any launch and every refusal leaves the context usable
+ * and the output untouched: GNSS_EARG for a null argument, n_taps, chip_off, a tap or post value,
+ * an unknown flag, n_chan, a PRN, n_rows, numSample outside 1..2^22, a non-finite state, codeFreq,
+ * an int16 record, GNSS_OUT_DEVICE without a context or with taps that is not device memory of
+ * the context's device, or a context of gnss_ctx_create_multi; GNSS_EIO for pos_bytes < 0, not a
+ * multiple of the sample size, or a read past the record's end; GNSS_EINDEX for a colon that has
+ * not numSample elements. */
+int gnss_replay_correlate(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *signal,
+                          const gnss_replay_cfg *cfg, const gnss_replay_rows *rows,
+                          gnss_replay_out *out);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
