@@ -311,6 +311,26 @@ class GnssReplayOut(C.Structure):
 ADDED_STRUCTS.update({"gnss_replay_cfg": "GnssReplayCfg", "gnss_replay_rows": "GnssReplayRows",
                       "gnss_replay_out": "GnssReplayOut"})
 
+# The two-path fit on any tap grid (gnss_acf_fit_taps / gnss_acf_fit_taps_window; additive within
+# ABI v13): gnss_acf_fit's grid with e up to 2.00 chips, for the wider grids of a replay; the taps'
+# coordinates u and the prompt's index come with the call
+ACF_FIT_TAPS_DEFAULTS = dict(ind_start=1, numOverLap=100, p_min=-0.40, p_step=0.01, p_count=81, e_min=0.05,
+                             e_step=0.01, e_count=196, ratio_max=1.0, gain_min=16.0)
+
+
+class GnssAcfFitTapsCfg(C.Structure):
+    _fields_ = [("n", C.c_int32), ("ind_start", C.c_int32), ("numOverLap", C.c_int32), ("n_taps", C.c_int32),
+                ("prompt", C.c_int32), ("flags", C.c_int32), ("u", C.c_void_p), ("p_min", C.c_double),
+                ("p_step", C.c_double), ("e_min", C.c_double), ("e_step", C.c_double), ("p_count", C.c_int32),
+                ("e_count", C.c_int32), ("ratio_max", C.c_double), ("gain_min", C.c_double)]
+
+
+class GnssAcfFitTapsIn(C.Structure):
+    _fields_ = [("taps", C.c_void_p), ("max_rows", C.c_int64), ("n_rows", C.c_void_p)]
+
+
+ADDED_STRUCTS.update({"gnss_acf_fit_taps_cfg": "GnssAcfFitTapsCfg", "gnss_acf_fit_taps_in": "GnssAcfFitTapsIn"})
+
 
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
@@ -455,6 +475,11 @@ PROTOTYPES = {
     "gnss_replay_correlate": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal),
                                         C.POINTER(GnssReplayCfg), C.POINTER(GnssReplayRows),
                                         C.POINTER(GnssReplayOut)]),
+    # the two-path fit on any tap grid (additive within ABI v13: detected by symbol)
+    "gnss_acf_fit_taps": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfFitTapsCfg), C.POINTER(GnssAcfFitTapsIn),
+                                    C.POINTER(GnssAcfFitOut)]),
+    "gnss_acf_fit_taps_window": (C.c_int, [C.POINTER(GnssAcfFitTapsCfg), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.POINTER(GnssAcfFitOut)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

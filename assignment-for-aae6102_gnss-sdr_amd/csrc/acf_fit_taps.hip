@@ -1,0 +1,131 @@
+// acf_fit_taps.hip — the two-path fit of an ACF on any tap grid over device-resident sums
+// (acf_fit_taps.h; GNSS_OUT_DEVICE), in the layout gnss_replay_correlate writes:
+// [n][2][n_taps][max_rows]. One kernel, one block of kThreads lanes per (channel, window), no
+// hand-off between blocks, two stages:
+//   1. the coherent sums. Up to 512 series (a tap's I or Q), each contiguous along the rows. The
+//      window is tiled over rows (kTile) and over groups of kGroup series, so the LDS need is a
+//      constant whatever numOverLap and n_taps are. Per row tile the rows' signs come from the
+//      prompt's I once and serve every series group. A group's tile is staged with lanes along the
+//      rows (a wave loads one series' 512-B run per step); then lanes 0..kGroup-1 add one series
+//      each, rows ascending, reading LDS at the odd row stride kStride (distinct banks) and the
+//      signs as broadcasts. A series' running sum waits in LDS (zs) between row tiles.
+//   2. the hypotheses. The tap coordinates (us) and the coherent vector (zs) stay in LDS and are
+//      read as broadcasts. The one-path hypotheses, then the two-path ones, are dealt over the
+//      lanes (lane t takes t, t + kThreads, ...); each lane keeps the lexicographic minimum of
+//      (res, index) of its share, the block takes the minimum of those by shuffles within a wave
+//      and through LDS across waves: a total order's minimum does not depend on the order it is
+//      taken in, so no float atomics are needed and two runs give the same bits. Lane 0 forms the
+//      winners' amplitudes again from their indices and stores the window's row.
+// Every sum runs over every tap: R = 0 outside a triangle is not exploited. Every loop is bounded
+// by values the host checked (acf_fit_taps.cpp). The arithmetic is acf_fit_taps.h's, shared with
+// the host path, without contraction: the outputs equal the host's bit for bit.
+#pragma clang fp contract(off)
+
+#include <hip/hip_runtime.h>
+
+#include "acf_fit_taps.h"
+
+namespace gnss {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kTile = 64;           // rows per LDS tile: one wave's load of one series
+constexpr int kStride = kTile + 1;  // doubles; odd: lanes along the series hit distinct banks
+constexpr int kGroup = 64;          // series per LDS tile: one wave adds them
+
+// the block's minimum of the lanes' (res, index), valid in lane 0 of the block; `wres` / `wh`
+// hold one entry per wave and are free again on return
+__device__ AcfFttBest block_best(AcfFttBest b, double* wres, int* wh)
+{
+    for (int off = 32; off; off >>= 1) {
+        const double r = __shfl_xor(b.res, off);
+        const int h = __shfl_xor(b.h, off);
+        ftt_best_merge(b, r, h);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wres[threadIdx.x >> 6] = b.res;
+        wh[threadIdx.x >> 6] = b.h;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int v = 1; v < kWaves; v++) ftt_best_merge(b, wres[v], wh[v]);
+    __syncthreads();
+    return b;
+}
+
+// window blockIdx.x of all channels' windows in channel order; its rows lie below n_rows[c] <=
+// max_rows (host check), so every load is inside channel c's series
+__global__ __launch_bounds__(kThreads) void acf_fit_taps_kernel(AcfFttDev d)
+{
+    __shared__ double tile[kGroup * kStride];
+    __shared__ double sg[kTile];             // the row tile's signs
+    __shared__ double zs[2 * kFttMaxTaps];   // zI[n_taps] then zQ[n_taps]
+    __shared__ double us[kFttMaxTaps];
+    __shared__ double wres[kWaves];
+    __shared__ int wh[kWaves];
+
+    const int tid = threadIdx.x;
+    const int64_t w = blockIdx.x;
+    int c = 0;
+    while (c + 1 < d.n && w >= d.win_base[c + 1]) c++;
+    const int64_t m = w - d.win_base[c];
+    const int64_t row = ftt_window_row(m, d.ind_start, d.numOverLap);
+    const int nt = d.grid.n_taps;
+    const int S = 2 * nt;  // the series: I then Q of every tap
+    const double* base = d.taps + (int64_t)c * S * d.max_rows + row;
+    const int N = (int)d.numOverLap;
+
+    // stage 1
+    for (int t0 = 0; t0 < N; t0 += kTile) {
+        const int nr = N - t0 < kTile ? N - t0 : kTile;
+        if (tid < nr) sg[tid] = ftt_sign(base[(int64_t)d.grid.prompt * d.max_rows + t0 + tid]);
+        for (int s0 = 0; s0 < S; s0 += kGroup) {
+            const int ns = S - s0 < kGroup ? S - s0 : kGroup;
+            for (int i = tid; i < ns * kTile; i += kThreads) {
+                const int s = i / kTile, r = i % kTile;
+                if (r < nr) tile[s * kStride + r] = base[(int64_t)(s0 + s) * d.max_rows + t0 + r];
+            }
+            __syncthreads();  // (the signs too, in the row tile's first group)
+            if (tid < ns) {
+                double acc = t0 ? zs[s0 + tid] : 0.0;
+                for (int r = 0; r < nr; r++) acc = ftt_accum(acc, sg[r], tile[tid * kStride + r], t0 + r == 0);
+                zs[s0 + tid] = acc;
+            }
+            __syncthreads();
+        }
+    }
+    for (int s = tid; s < S; s += kThreads)
+        if (d.z) d.z[w * S + s] = zs[s];
+    for (int j = tid; j < nt; j += kThreads) us[j] = d.u[j];
+    __syncthreads();
+
+    // stage 2
+    const double* zI = zs;
+    const double* zQ = zs + nt;
+    AcfFttBest b1 = ftt_best_none(), b2 = ftt_best_none();
+    if (ftt_all_finite(nt, zI, zQ)) {  // (uniform over the block)
+        for (int ip = tid; ip < d.grid.p_count; ip += kThreads)
+            ftt_best_take(b1, ftt_one(nt, us, zI, zQ, ftt_p(d.grid, ip)), ip);
+        const int H = d.grid.p_count * d.grid.e_count;
+#pragma unroll 1
+        for (int h = tid; h < H; h += kThreads) ftt_best_take(b2, ftt_two_at(d.grid, us, zI, zQ, h), h);
+    }
+    b1 = block_best(b1, wres, wh);
+    b2 = block_best(b2, wres, wh);
+    if (tid == 0) {
+        reinterpret_cast<AcfFttRow*>(d.rows)[w] = ftt_select(d.grid, us, zI, zQ, b1.h, b2.h);
+    }
+}
+
+}  // namespace
+
+int acf_fit_taps_launch(const AcfFttDev& d, void* stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t total = d.win_base[d.n];
+    if (total > 0) hipLaunchKernelGGL(acf_fit_taps_kernel, dim3((unsigned)total), dim3(kThreads), 0, stream, d);
+    return (int)hipGetLastError();
+}
+
+}  // namespace gnss

@@ -1767,3 +1767,117 @@ def replay_coherent(taps_out, prompt, rows_per_window: int):
     sign = np.where(p[:, : nwin * w] < 0, -1.0, 1.0)
     z = t[:, :, :, : nwin * w] * sign[:, None, None, :]
     return z.reshape(t.shape[0], 2, t.shape[2], nwin, w).sum(axis=4)
+
+
+# ---------------------------------------------------------------------------
+# The two-path fit on any tap grid, fed by the replay (gnss_acf_fit_taps)
+# ---------------------------------------------------------------------------
+def acf_fit_taps(taps_out, n_rows, u, prompt=None, *, ctx: Context | None = None, want_acf: bool = False, **params):
+    """acf_fit's two-path fit for sums on any tap grid (gnss_acf_fit_taps): per window of
+    numOverLap rows a direct path plus one reflected path fitted to the coherently summed
+    correlation function at the coordinates `u`. Returns acf_fit's namespace without prn and
+    orient: windows [n] and, per name, a list of n arrays with one value per window -- paths, bias,
+    bias_m, p1, A1p_re, A1p_im, res1, p0, e, A0_re, A0_im, A1_re, A1_im, res2, ratio, dphi_cycles,
+    energy, with want_acf also zI, zQ [n_taps][windows] per channel -- plus u, prompt and
+    kernel_ms (0 on the host path).
+
+    `taps_out` [n, 2, n_taps, max_rows] as replay_correlate returns it: a numpy array (the host
+    path, no GPU needed) or a torch tensor on the context's device, read where it lies by the
+    kernel (device_out=True: only the fit rows leave HBM). `n_rows` [n]: the rows of each channel.
+    `u` [n_taps]: the taps' coordinates in chips, a later path at a lower u; for replayed sums the
+    tap offsets as they are. `prompt`: the index of the tap whose I gives a row's sign; None takes
+    the one tap with u == 0. params: ind_start, numOverLap, the grid p_min, p_step, p_count, e_min,
+    e_step, e_count, and ratio_max, gain_min (abi.ACF_FIT_TAPS_DEFAULTS); cSpeed and
+    codeFreqBasis for bias_m."""
+    cSpeed = float(params.pop("cSpeed", 299792458.0))
+    codeFreqBasis = float(params.pop("codeFreqBasis", 1.023e6))
+    unknown = set(params) - set(abi.ACF_FIT_TAPS_DEFAULTS)
+    if unknown:
+        raise TypeError(f"acf_fit_taps: unknown parameter(s) {sorted(unknown)}")
+    par = dict(abi.ACF_FIT_TAPS_DEFAULTS, **params)
+    uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    nt = len(uu)
+    if prompt is None:
+        zero = np.flatnonzero(uu == 0)
+        if len(zero) != 1:
+            raise ValueError(f"acf_fit_taps: {len(zero)} taps have u == 0; name the prompt tap")
+        prompt = int(zero[0])
+    on_device = hasattr(taps_out, "data_ptr")
+    if on_device:
+        if ctx is None:
+            raise ValueError("acf_fit_taps: a device tensor needs a Context")
+        torch = abi.require_torch()
+        t = taps_out
+        if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda or t.device.index != ctx.device:
+            raise ValueError("acf_fit_taps: the tensor is contiguous float64 on the context's device")
+        torch.cuda.current_stream(t.device).synchronize()
+        ptr = t.data_ptr()
+    else:
+        t = np.ascontiguousarray(taps_out, dtype=np.float64)
+        ptr = t.ctypes.data
+    if t.ndim != 4 or t.shape[1] != 2 or t.shape[2] != nt:
+        raise ValueError("acf_fit_taps: taps_out is [n, 2, n_taps, max_rows] with one u per tap")
+    n, max_rows = int(t.shape[0]), int(t.shape[3])
+    if n > abi.VT_MAX_CH:
+        raise ValueError(f"acf_fit_taps takes at most {abi.VT_MAX_CH} channels")
+    nr = np.ascontiguousarray(n_rows, dtype=np.int64).reshape(-1)
+    if len(nr) != n:
+        raise ValueError("acf_fit_taps: n_rows has one value per channel")
+    cfg = abi.GnssAcfFitTapsCfg()
+    cfg.n, cfg.n_taps, cfg.prompt = n, nt, int(prompt)
+    cfg.u = uu.ctypes.data
+    cfg.flags = abi.OUT_DEVICE if on_device else 0
+    for k in ("ind_start", "numOverLap", "p_count", "e_count"):
+        setattr(cfg, k, int(par[k]))
+    for k in ("p_min", "p_step", "e_min", "e_step", "ratio_max", "gain_min"):
+        setattr(cfg, k, float(par[k]))
+    src = abi.GnssAcfFitTapsIn()
+    src.taps, src.max_rows, src.n_rows = ptr, max_rows, nr.ctypes.data
+    nov = max(cfg.numOverLap, 1)
+    cap = max([max(int(l) - cfg.ind_start, 0) // nov for l in nr] + [1])
+    out = abi.GnssAcfFitOut()
+    out.cap = cap
+    windows = np.zeros(max(n, 1), dtype=np.int64)
+    out.windows = windows.ctypes.data_as(C.POINTER(C.c_int64))
+    paths = np.zeros((max(n, 1), cap), dtype=np.int32)
+    out.paths = paths.ctypes.data_as(C.POINTER(C.c_int32))
+    arr = {f: np.zeros((max(n, 1), cap)) for f in abi.ACF_FIT_FIELDS}
+    if want_acf:
+        arr["zI"], arr["zQ"] = np.zeros((max(n, 1), nt, cap)), np.zeros((max(n, 1), nt, cap))
+    for f, a in arr.items():
+        setattr(out, f, a.ctypes.data_as(C.POINTER(C.c_double)))
+    lib = abi.load()
+    h = ctx.h if ctx is not None else None
+    st = lib.gnss_acf_fit_taps(h, C.byref(cfg), C.byref(src), C.byref(out))
+    if st != abi.OK:
+        msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
+        raise abi.GnssError(st, msg)
+    res = SimpleNamespace(windows=windows[:n].copy(), u=uu, prompt=int(prompt),
+                          kernel_ms=float(ctx.timing()["track_kernel_ms"]) if on_device else 0.0,
+                          paths=[paths[c, : windows[c]].copy() for c in range(n)])
+    for f, a in arr.items():
+        setattr(res, f, [a[c, ..., : windows[c]].copy() for c in range(n)])
+    res.bias_m, res.ratio, res.dphi_cycles = [], [], []
+    for c in range(n):
+        a0 = res.A0_re[c] + 1j * res.A0_im[c]
+        a1 = res.A1_re[c] + 1j * res.A1_im[c]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            res.bias_m.append(res.bias[c] * cSpeed / codeFreqBasis)
+            res.ratio.append(np.abs(a1) / np.abs(a0))
+            res.dphi_cycles.append(np.angle(a1 * np.conj(a0)) / (2 * np.pi))
+    return res
+
+
+def replay_fit(file, signal, rows, taps, *, chip_off: int = 0, post=None, ctx: Context | None = None, **params):
+    """replay_correlate on `taps`, then acf_fit_taps with u = taps on the replayed sums: the
+    multipath delay estimate on a grid of the caller's choice (a ray more than 0.6 chip late is in
+    none of the 25-tap records). With a Context both steps run on the GPU and the sums stay in
+    HBM between them (GNSS_OUT_DEVICE): only the fit rows come back. Returns acf_fit_taps'
+    namespace with kernel_ms = (the replay's, the fit's). params: acf_fit_taps' (prompt, want_acf,
+    the windows, the grid and the thresholds)."""
+    tp = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+    sums, replay_ms = replay_correlate(file, signal, rows, tp, chip_off=chip_off, post=post, ctx=ctx,
+                                       device_out=ctx is not None)
+    res = acf_fit_taps(sums, rows.n_rows, tp, params.pop("prompt", None), ctx=ctx, **params)
+    res.kernel_ms = (float(replay_ms), res.kernel_ms)
+    return res

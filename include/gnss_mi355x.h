@@ -1178,6 +1178,65 @@ int gnss_replay_correlate(gnss_ctx *ctx, const gnss_file *file, const gnss_signa
                           const gnss_replay_cfg *cfg, const gnss_replay_rows *rows,
                           gnss_replay_out *out);
 
+/* ---- two-path fit of an ACF on any tap grid (additive within ABI v13; detected by symbol) ---
+ * gnss_acf_fit's estimator for the sums gnss_replay_correlate writes: a reflected ray whose
+ * triangle lies outside the 25 taps' +-0.6 chip can be replayed on a wider grid and then fitted.
+ * The definition is gnss_acf_fit's (the comment above gnss_acf_fit_cfg) with three substitutions
+ * and nothing else (csrc/acf_fit_taps.h is the one source for host and device):
+ *   - 25 becomes n_taps, 1..GNSS_REPLAY_MAX_TAPS;
+ *   - the prompt index 12 becomes `prompt`, 0..n_taps-1: the tap whose I sum of the same row
+ *     gives the row's sign s_r (>= 0: +1, otherwise -1; a NaN gives -1);
+ *   - u[j] = (orient*(j-12))*corrSpacing becomes u[j] as the caller gives it: finite, in any
+ *     order, uniform or not, in orient = +1's convention (a path that arrives later sits at a
+ *     lower u). For replayed sums u = tap_offsets as they are.
+ * The windows, the first row's term taken as it is, every sum left to right from its first term
+ * over all n_taps taps, the skip rules, the smallest (res, index), paths = 0 / 1 / 2 and the NaN
+ * outputs carry over. With n_taps = 25, prompt = 12 and u[j] = (orient*(j-12))*corrSpacing every
+ * output equals gnss_acf_fit's bit for bit, on the host and on the GPU. */
+typedef struct gnss_acf_fit_taps_cfg {
+    int32_t       n;            /* channels, 1..GNSS_VT_MAX_CH                                  */
+    int32_t       ind_start;    /* as gnss_acf_cfg, >= 1; default 1                             */
+    int32_t       numOverLap;   /* rows per window, 2..4096; default 100                        */
+    int32_t       n_taps;       /* 1..GNSS_REPLAY_MAX_TAPS                                      */
+    int32_t       prompt;       /* 0..n_taps-1                                                  */
+    int32_t       flags;        /* GNSS_OUT_DEVICE: in->taps is a DEVICE pointer, or 0          */
+    const double *u;            /* [n_taps] tap coordinates in chips, host, finite              */
+    double        p_min, p_step;      /* default -0.40, 0.01                                    */
+    double        e_min, e_step;      /* default 0.05, 0.01                                     */
+    int32_t       p_count, e_count;   /* default 81, 196; each >= 1, p_count*e_count <= 65536   */
+    double        ratio_max;    /* default 1.0                                                  */
+    double        gain_min;     /* default 16.0                                                 */
+} gnss_acf_fit_taps_cfg;
+
+typedef struct gnss_acf_fit_taps_in {
+    const double  *taps;        /* [n][2][n_taps][max_rows], gnss_replay_out.taps' layout: a host
+                                   array, or with GNSS_OUT_DEVICE device memory of the context's
+                                   device                                                       */
+    int64_t        max_rows;    /* >= 1                                                         */
+    const int64_t *n_rows;      /* [n] host, each 0..max_rows: channel c's windows lie below it */
+} gnss_acf_fit_taps_in;
+
+/* The fit over replayed sums. out: gnss_acf_fit's struct, zI / zQ (optional) [n][n_taps][cap].
+ * Host sums need no GPU and ctx may be NULL (up to 16 threads, a window by one thread: the bits do
+ * not depend on the thread count); with GNSS_OUT_DEVICE the fit runs on the GPU
+ * (csrc/acf_fit_taps.hip, one block per window) and gnss_last_timing's track_kernel_ms holds the
+ * kernel's duration. Both paths give the same bits in every output. Everything is checked on the
+ * host before any launch; each refusal sets the error text and leaves the outputs untouched and
+ * the context usable. GNSS_EARG for a null argument, n, n_taps or prompt out of range, a
+ * non-finite u[j], numOverLap outside 2..4096, ind_start < 1, p_step or e_step not positive, a
+ * non-finite p_min or e_min, a count below 1, p_count*e_count > 65536, a ratio_max or gain_min
+ * that is negative or NaN, max_rows < 1, n_rows[c] outside 0..max_rows, more windows than cap, an
+ * unknown flag, GNSS_OUT_DEVICE without a context or with taps that is not device memory of the
+ * context's device, and device sums on a context of gnss_ctx_create_multi. */
+int gnss_acf_fit_taps(gnss_ctx *ctx, const gnss_acf_fit_taps_cfg *cfg,
+                      const gnss_acf_fit_taps_in *in, gnss_acf_fit_out *out);
+
+/* The fit alone on one coherent vector zI[n_taps], zQ[n_taps], host only: cfg's n_taps, u, grid
+ * and thresholds are read (n, ind_start, numOverLap, prompt beyond its range check and flags are
+ * not); out as for gnss_acf_fit_window, zI / zQ, if given, get the vector at [j * cap]. */
+int gnss_acf_fit_taps_window(const gnss_acf_fit_taps_cfg *cfg, const double *zI, const double *zQ,
+                             gnss_acf_fit_out *out);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
