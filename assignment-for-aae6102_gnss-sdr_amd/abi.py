@@ -387,6 +387,9 @@ PROTOTYPES = {
     "gnss_acquisition": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal),
                                    C.POINTER(GnssAcq), C.POINTER(GnssAcquired),
                                    C.POINTER(GnssAcqDiag)]),
+    "gnss_acquisition_surface": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal),
+                                           C.POINTER(GnssAcq), C.POINTER(C.c_double),
+                                           C.POINTER(GnssAcqDiag)]),
     "gnss_tracking_ct": (C.c_int, [C.c_void_p, C.POINTER(GnssFile), C.POINTER(GnssSignal),
                                    C.POINTER(GnssTrack), C.POINTER(GnssAcquired),
                                    C.POINTER(GnssTrackOut)]),

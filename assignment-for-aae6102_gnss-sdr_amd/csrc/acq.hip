@@ -44,15 +44,15 @@ __global__ void acq_wipe_kernel(const Src src, int64_t S, int datalen, int nbins
     const double f = (IF + (freqMin + freqStep * (double)b)) / Fs;  // cycles per sample
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < S;
          n += (int64_t)gridDim.x * blockDim.x) {
-        double cyc = f * (double)(n + 1);
-        cyc -= floor(cyc);
         R c, s;
         if constexpr (sizeof(R) == 4) {
+            double cyc = f * (double)(n + 1);
+            cyc -= floor(cyc);
             const float ph = (float)cyc;
             c = cos_rev(ph);
             s = sin_rev(ph);
-        } else {
-            sincospi(2.0 * cyc, &s, &c);
+        } else {  // the reference's own rounding of the angle (acq_carrier_angle)
+            sincos(acq_carrier_angle(IF, freqMin, freqStep, b, n + 1, Fs), &s, &c);
         }
         const double2 x = src.at((int64_t)idx * S + n);
         const R xr = (R)x.x, xi = (R)x.y;

@@ -503,15 +503,15 @@ __global__ __launch_bounds__(kRowThreads) void fwd_rows_kernel(
         const double f = (IF + (freqMin + freqStep * (double)bin)) / Fs;  // cycles per sample
         auto put = [&](int n1, double2 r) {
             const int64_t n = (int64_t)P * n1 + n2;
-            double cyc = f * (double)(n + 1);  // n is 1-based in the reference
-            cyc -= floor(cyc);
             R c, sn;
             if constexpr (sizeof(R) == 4) {
+                double cyc = f * (double)(n + 1);  // n is 1-based in the reference
+                cyc -= floor(cyc);
                 const float ph = (float)cyc;
                 c = __builtin_amdgcn_cosf(ph);
                 sn = __builtin_amdgcn_sinf(ph);
-            } else {
-                sincospi(2.0 * cyc, &sn, &c);
+            } else {  // the reference's own rounding of the angle (acq_carrier_angle)
+                sincos(acq_carrier_angle(IF, freqMin, freqStep, bin, n + 1, Fs), &sn, &c);
             }
             const R xr = (R)r.x, xi = (R)r.y;
             s_a[n1] = mk<V>(fma2(xr, c, -(xi * sn)), fma2(xr, sn, xi * c));

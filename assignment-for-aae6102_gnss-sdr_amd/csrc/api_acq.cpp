@@ -269,16 +269,28 @@ static int group_acquisition(gnss_ctx* g, const gnss_file* file, const gnss_sign
     return status;
 }
 
-extern "C" {
+namespace {
+// What the coarse half of the acquisition hands to what follows it, while its buffers, its IF
+// window and its events are alive.
+struct AcqCoarse {
+    const int8_t* blk;   // the staged IF bytes at the block's first sample
+    const double2* xf;   // the fine block's samples (formats other than int8 I/Q), or nullptr
+    int64_t flen, off, bps, S;
+    int np, nb, dl, L, dtyp;
+    bool iq8;
+    int dbl, perm;       // the surface's precision and storage order (perm = P: tau2-major)
+    const void* corr;    // the surface on the device: [np][nb][S] double (dbl) or float
+    Events &e_conv, &e_all, &e_corr;
+};
 
-// ---------------------------------------------------------------------------
-// acquisition.m
-// ---------------------------------------------------------------------------
-int gnss_acquisition(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg,
-                     const gnss_acq* acq, gnss_acquired* out, gnss_acq_diag* diag)
+// acquisition.m:27-80: read block -> PRN x bin x ms search -> detector -> threshold into *out and
+// *diag, then rest(AcqCoarse) on the same stream (gnss_acquisition: the fine search;
+// gnss_acquisition_surface: the surface's download). One body, so both entries issue the same
+// launches, allocations and events up to that point.
+template <class Rest>
+int acq_coarse(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg, const gnss_acq* acq, gnss_acquired* out,
+               gnss_acq_diag* diag, Rest&& rest)
 {
-    if (!ctx || !file || !sg || !acq || !out) return GNSS_EARG;
-    if (!ctx->members.empty()) return group_acquisition(ctx, file, sg, acq, out, diag);
     memset(out, 0, sizeof(*out));
     if (diag) memset(diag, 0, sizeof(*diag));
     ctx->timing = gnss_timing{};
@@ -392,6 +404,22 @@ int gnss_acquisition(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg
             acq_idx.push_back(i);
         }
     }
+    const AcqCoarse c{blk, xf, flen, off, bps, S, np, nb, dl, L, dtyp, iq8, dbl, perm, corr.p, e_conv, e_all, e_corr};
+    return rest(c);
+}
+
+// gnss_acquisition after its coarse half: the empty result (acquisition.m:84-85) or the fine
+// frequency of every acquired SV (:89-126) into out->fineFreq, and the call's timing.
+int acq_fine(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg, gnss_acquired* out,
+                    const AcqCoarse& c)
+{
+    const int8_t* blk = c.blk;
+    const double2* xf = c.xf;
+    const int64_t flen = c.flen, off = c.off, bps = c.bps, S = c.S;
+    const int dl = c.dl, L = c.L, dtyp = c.dtyp;
+    const bool iq8 = c.iq8;
+    Events &e_conv = c.e_conv, &e_all = c.e_all, &e_corr = c.e_corr;
+    int st = GNSS_OK;
     if (out->n == 0) {
         HIP_TRY(hipEventRecord(e_all.b, ctx->stream));
         HIP_TRY(hipEventSynchronize(e_all.b));
@@ -462,6 +490,58 @@ int gnss_acquisition(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg
     ctx->timing.acq_fine_ms = e_fine.ms();
     ctx->timing.acq_ms = e_all.ms() + (iq8 ? 0.0 : e_conv.ms());
     return GNSS_OK;
+}
+
+// gnss_acquisition_surface after the same coarse half: corr back to the host, widened to double
+// and, where the own correlator stored it tau2-major (perm = P: storage k holds column
+// k / 2000 + P * (k % 2000), acq.hip natural_col), put in natural column order.
+int acq_surface_out(gnss_ctx* ctx, double* surface_out, const AcqCoarse& c)
+{
+    const size_t cells = (size_t)c.np * c.nb * (size_t)c.S;
+    std::vector<char> h(cells * (c.dbl ? sizeof(double) : sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(h.data(), c.corr, h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipEventRecord(c.e_all.b, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->timing.acq_corr_ms = c.e_all.ms();
+    ctx->timing.acq_ms = ctx->timing.acq_corr_ms + (c.iq8 ? 0.0 : c.e_conv.ms());
+    const double* hd = reinterpret_cast<const double*>(h.data());
+    const float* hf = reinterpret_cast<const float*>(h.data());
+    const int64_t S = c.S;
+    parallel_for(c.np * c.nb, [&](int r) {
+        double* o = surface_out + (size_t)r * S;
+        for (int64_t k = 0; k < S; k++) {
+            const int64_t col = c.perm ? k / 2000 + (int64_t)c.perm * (k % 2000) : k;
+            o[col] = c.dbl ? hd[(size_t)r * S + k] : (double)hf[(size_t)r * S + k];
+        }
+    });
+    return GNSS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// acquisition.m
+// ---------------------------------------------------------------------------
+int gnss_acquisition(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg,
+                     const gnss_acq* acq, gnss_acquired* out, gnss_acq_diag* diag)
+{
+    if (!ctx || !file || !sg || !acq || !out) return GNSS_EARG;
+    if (!ctx->members.empty()) return group_acquisition(ctx, file, sg, acq, out, diag);
+    return acq_coarse(ctx, file, sg, acq, out, diag,
+                      [&](const AcqCoarse& c) { return acq_fine(ctx, file, sg, out, c); });
+}
+
+// The parity hook of the correlation surface (tests): gnss_acquisition's coarse half under the
+// context's precision and options, then the whole surface in natural column order; no fine search.
+int gnss_acquisition_surface(gnss_ctx* ctx, const gnss_file* file, const gnss_signal* sg, const gnss_acq* acq,
+                             double* surface_out, gnss_acq_diag* diag)
+{
+    if (!ctx || !file || !sg || !acq || !surface_out) return GNSS_EARG;
+    if (!ctx->members.empty()) return fail(ctx, GNSS_EARG, "gnss_acquisition_surface: single-device contexts only");
+    gnss_acquired acquired;  // (the 12 dB gate's list: not reported here)
+    return acq_coarse(ctx, file, sg, acq, &acquired, diag,
+                      [&](const AcqCoarse& c) { return acq_surface_out(ctx, surface_out, c); });
 }
 
 }  // extern "C"

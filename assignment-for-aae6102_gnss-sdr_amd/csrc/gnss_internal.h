@@ -558,6 +558,19 @@ size_t prefix16_scratch_bytes(int64_t ngroups);
 hipError_t launch_prefix16(const short* src, int64_t ngroups, long long* pref_i, long long* pref_q,
                            void* scratch, size_t scratch_bytes, hipStream_t s);
 
+// The angle of carrier(b, n) = exp(1i*2*pi*(IF + dopplershift(b))*n./Fs), n 1-based, rounded
+// step by step as acquisition.m:41-44 rounds it: (2 pi (IF + f_b) * n) / Fs in radians. At IF =
+// 4.58 MHz it reaches 2.9e4 rad, where an ulp is 3.6e-12 rad: an angle reduced in cycles first is
+// nearer the exact carrier and 1e-11 of the RMS away from the reference's surface
+// (tests/test_gpu_acq_surface.py). Defined here, outside acq_fft.hip's fp contract(fast), so
+// both fp64 wipe kernels round it alike: separate multiplies, one division.
+__device__ __forceinline__ double acq_carrier_angle(double IF, double freqMin, double freqStep, int bin, int64_t n,
+                                                    double Fs)
+{
+    const double w = (2.0 * 3.14159265358979323846) * (IF + (freqMin + freqStep * (double)bin));
+    return (w * (double)n) / Fs;
+}
+
 // The acquisition kernels' sample source: the record's int8 I/Q bytes, or an fp64
 // complex staging of another format (launch_stage_cpx).
 struct SrcIQ8 {

@@ -421,6 +421,28 @@ def acquisition(file, signal, acq, *, ctx: Context | None = None, prn_list=None,
     return res
 
 
+def acquisition_surface(file, signal, acq, *, ctx: Context | None = None, prn_list=None):
+    """The acquisition's whole correlation surface (gnss_acquisition_surface, a parity hook):
+    the coarse half of `acquisition` under the context's precision and options, no fine search.
+    Returns (surface[np, freqNum, Sample] in natural column order, as float64; the per-PRN
+    detector diagnostics the same call computed from it)."""
+    ctx = ctx or default_context()
+    f, k1 = to_c_file(file)
+    s = to_c_signal(signal)
+    a, k2 = to_c_acq(acq, prn_list)
+    npr = len(prn_list) if prn_list is not None else 32
+    surf = np.zeros((npr, int(acq.freqNum), int(signal.Sample)))
+    dg = abi.GnssAcqDiag()
+    st = ctx.lib.gnss_acquisition_surface(ctx.h, C.byref(f), C.byref(s), C.byref(a),
+                                          surf.ctypes.data_as(C.POINTER(C.c_double)), C.byref(dg))
+    ctx.check(st)
+    n = dg.n
+    d = SimpleNamespace(prn=np.array(dg.prn[:n]), SNR=np.array(dg.SNR[:n]),
+                        fbin=np.array(dg.fbin[:n]), codePhase=np.array(dg.codePhase[:n]),
+                        peak=np.array(dg.peak[:n]), peak2=np.array(dg.peak2[:n]))
+    return surf, d
+
+
 def trackingCT(file, signal, track, Acquired, *, ctx: Context | None = None, taps=None,
                channels=None, save_countinx: str | None = None, raw: bool = False,
                out: "TrackOutBuffers | None" = None):

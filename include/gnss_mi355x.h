@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNSS_ABI_VERSION 13
+#define GNSS_ABI_VERSION 14
 
 /* ---- status codes (SURVEY §8b "Error conventions") --------------------- */
 #define GNSS_OK         0
@@ -435,6 +435,20 @@ int gnss_correlate_step(gnss_ctx *ctx, const gnss_file *file, const gnss_signal 
                         double remPhase, int64_t pos_bytes, int n_taps, const double *taps,
                         double *sums_out, int64_t *numSample_out);
 
+/* Parity hook (ABI v14): the acquisition's whole correlation surface, for tests that compare
+ * every cell with an independent evaluation of acquisition.m:41-61. Runs gnss_acquisition's
+ * own coarse half (the same staging, the same correlator under the context's precision and
+ * GNSS_OPT_ACQ_* options, the same detector), then copies the surface back:
+ *   surface_out[(p * freqNum + b) * Sample + tau], p over the PRN list, b the Doppler bin, tau
+ *   the code-phase column in natural order (the own correlator's tau2-major storage is undone
+ *   on the host); an fp32 surface (gnss_ctx_set_acq_precision(ctx, 0)) is widened to double.
+ * diag (may be NULL) is filled as gnss_acquisition fills it, from that same surface. No fine
+ * search runs, and GNSS_OK is returned also when no PRN clears the 12 dB gate. Single-device
+ * contexts only (GNSS_EARG on a multi-device one). Not a product path: the surface crosses
+ * PCIe and is reordered by the host.                                                        */
+int gnss_acquisition_surface(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *signal,
+                             const gnss_acq *acq, double *surface_out, gnss_acq_diag *diag);
+
 /* ---- trackingVT_POS_updated.m, the tracking half (ABI v9) -----------
  * Steps of the loop at trackingVT_POS_updated.m:157-349 for n channels: read sizing (:161),
  * the three replica chips, the carrier wipe and sums (:217-281), the remaining code /
@@ -654,7 +668,7 @@ int gnss_tracking_vt(gnss_ctx *ctx, const gnss_file *file, const gnss_signal *si
 
 /* ---- trackingVT_POS_updated_multicorrelator.m: the 25-tap vector-tracking loop ------------
  * Additive within ABI v13: new symbols and one new struct, no existing layout or meaning
- * changes and gnss_abi_version() stays 13; a caller detects these entry points by symbol
+ * changes and gnss_abi_version() stayed 13; a caller detects these entry points by symbol
  * (dlsym / hasattr). Line cites below are of trackingVT_POS_updated_multicorrelator.m.
  *
  * The loop SDR_main.m runs for cmn.mltCorrON = [1 1]. It is trackingVT_POS_updated.m except:
@@ -726,7 +740,7 @@ int gnss_vt_mc_nav_update(gnss_vt_nav *nav, const double *codeError, const doubl
 
 /* ---- trackingCT_POS_updated.m, the positioning half: navSolutionsCT ---------------------------
  * Additive within ABI v13, like the 25-tap loop above: one status, two structs and one entry
- * point, no existing layout or meaning changes and gnss_abi_version() stays 13; a caller detects
+ * point, no existing layout or meaning changes and gnss_abi_version() stayed 13; a caller detects
  * the entry point by symbol. Line cites are of trackingCT_POS_updated.m unless marked.
  *
  * Positioning does not feed back into the scalar loops, so it runs as a pass over the records of

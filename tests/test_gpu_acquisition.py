@@ -30,6 +30,10 @@ def compare(g, gd, r, rd, prec="fp64"):
     assert np.array_equal(gd.fbin, rd.fbin), (gd.fbin, rd.fbin)
     assert np.array_equal(gd.codePhase, rd.codePhase)
     assert np.max(np.abs(gd.SNR - rd.SNR)) < SNR_TOL[prec], np.max(np.abs(gd.SNR - rd.SNR))
+    # peak and peak2 against the oracle too: the SNR's tolerance as a ratio
+    ratio_tol = 10 ** (SNR_TOL[prec] / 10) - 1
+    assert np.max(np.abs(gd.peak / rd.peak - 1)) < ratio_tol, np.max(np.abs(gd.peak / rd.peak - 1))
+    assert np.max(np.abs(gd.peak2 / rd.peak2 - 1)) < ratio_tol, np.max(np.abs(gd.peak2 / rd.peak2 - 1))
     assert np.array_equal(g.sv, r.sv)
     assert np.array_equal(g.codedelay, r.codedelay)
     assert np.array_equal(g.Doppler, r.Doppler)

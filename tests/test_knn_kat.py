@@ -175,7 +175,7 @@ def test_every_refusal(pkg):
         bad[7, 2] = v
         assert K.standardize(pkg, bad)[0] == abi.EARG
     assert K.standardize(pkg, np.full((2, 1), 1.7e308))[0] == abi.EARG  # the column's sum overflows: mu
-    assert ok() == abi.OK and lib.gnss_abi_version() == 13
+    assert ok() == abi.OK and lib.gnss_abi_version() == 14
 
 
 def test_python_layer(pkg):

@@ -122,7 +122,7 @@ def test_struct_sizes_and_version(pkg, tmp_path):
         for fname, _ in st._fields_:
             assert int(got[f"{cname}.{fname}"]) == getattr(st, fname).offset, (cname, fname)
     assert int(got["GNSS_MAX_RAYS"]) == pkg.abi.MAX_RAYS == 128
-    assert int(got["GNSS_ABI_VERSION"]) == 13 and pkg.abi.load().gnss_abi_version() == 13
+    assert int(got["GNSS_ABI_VERSION"]) == 14 and pkg.abi.load().gnss_abi_version() == 14
 
 
 def test_add_ray_and_scene_of(pkg):

@@ -225,7 +225,7 @@ def test_multicorrelator_update_uses_minus_if(pkg, po):
 
 def test_added_struct_layout_matches_header(pkg):
     """The structs added within ABI v13 (abi.ADDED_STRUCTS), checked as test_abi checks the
-    older ones: size and every field's offset against the header; the version stays 13."""
+    older ones: size and every field's offset against the header; they did not move the version (14 since gnss_acquisition_surface)."""
     header = os.path.join(ROOT, "include", "gnss_mi355x.h")
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{header}"', "int main(){"]
     for cname, pyname in pkg.abi.ADDED_STRUCTS.items():
@@ -244,5 +244,5 @@ def test_added_struct_layout_matches_header(pkg):
         assert int(got[cname]) == C.sizeof(st), cname
         for fname, _ in st._fields_:
             assert int(got[f"{cname}.{fname}"]) == getattr(st, fname).offset, (cname, fname)
-    assert pkg.abi.load().gnss_abi_version() == 13
+    assert pkg.abi.load().gnss_abi_version() == 14
     assert pkg.abi.GnssVtMcOut._fields_[: len(pkg.abi.GnssVtOut._fields_)] == pkg.abi.GnssVtOut._fields_
