@@ -331,6 +331,33 @@ class GnssAcfFitTapsIn(C.Structure):
 
 ADDED_STRUCTS.update({"gnss_acf_fit_taps_cfg": "GnssAcfFitTapsCfg", "gnss_acf_fit_taps_in": "GnssAcfFitTapsIn"})
 
+# The delay-Doppler map over replayed rows (gnss_replay_ddm; additive within ABI v14): a window's
+# rows summed coherently with one rotation per row, per (tap, Doppler offset) cell, and its peaks
+DDM_MAX_DOPP = 256
+DDM_MAP_DEVICE = 2  # with OUT_DEVICE: out.map is device memory and stays there
+
+
+class GnssReplayDdmCfg(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_taps", C.c_int32), ("prompt", C.c_int32), ("rows_per_window", C.c_int32),
+                ("n_dopp", C.c_int32), ("flags", C.c_int32), ("dopp_hz", C.c_void_p), ("u", C.c_void_p),
+                ("excl_chips", C.c_double), ("excl_hz", C.c_double), ("Fs", C.c_double),
+                ("bytes_per_sample", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GnssReplayDdmIn(C.Structure):
+    _fields_ = [("taps", C.c_void_p), ("max_rows", C.c_int64), ("n_rows", C.c_void_p), ("pos_bytes", C.c_void_p),
+                ("numSample", C.c_void_p)]
+
+
+class GnssReplayDdmOut(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("map", C.c_void_p), ("peak_bin", C.c_void_p), ("peak_tap", C.c_void_p),
+                ("peak_pow", C.c_void_p), ("sec_bin", C.c_void_p), ("sec_tap", C.c_void_p), ("sec_pow", C.c_void_p),
+                ("n_win", C.c_void_p), ("kernel_ms", C.c_double)]
+
+
+ADDED_STRUCTS.update({"gnss_replay_ddm_cfg": "GnssReplayDdmCfg", "gnss_replay_ddm_in": "GnssReplayDdmIn",
+                      "gnss_replay_ddm_out": "GnssReplayDdmOut"})
+
 
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
@@ -483,6 +510,9 @@ PROTOTYPES = {
                                     C.POINTER(GnssAcfFitOut)]),
     "gnss_acf_fit_taps_window": (C.c_int, [C.POINTER(GnssAcfFitTapsCfg), C.POINTER(C.c_double),
                                            C.POINTER(C.c_double), C.POINTER(GnssAcfFitOut)]),
+    # the delay-Doppler map over replayed rows (additive within ABI v14: detected by symbol)
+    "gnss_replay_ddm": (C.c_int, [C.c_void_p, C.POINTER(GnssReplayDdmCfg), C.POINTER(GnssReplayDdmIn),
+                                  C.POINTER(GnssReplayDdmOut)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

@@ -1903,3 +1903,102 @@ def replay_fit(file, signal, rows, taps, *, chip_off: int = 0, post=None, ctx: C
     res = acf_fit_taps(sums, rows.n_rows, tp, params.pop("prompt", None), ctx=ctx, **params)
     res.kernel_ms = (float(replay_ms), res.kernel_ms)
     return res
+
+
+# ---------------------------------------------------------------------------
+# The delay-Doppler map over replayed rows (gnss_replay_ddm)
+# ---------------------------------------------------------------------------
+def replay_ddm(taps_out, rows, dopp_hz, *, u, prompt, rows_per_window: int, signal, file, ctx: Context | None = None,
+               want_map: bool = True, device_out: bool = False, excl_chips: float = 0.3, excl_hz: float = 10.0):
+    """The delay-Doppler map of every window of rows_per_window consecutive rows of a replay: per
+    tap and per Doppler offset the window's rows summed coherently with one rotation per row, held
+    at the row's middle sample -- the correlation the loop would have seen with its carrier
+    dopp_hz[m] higher (gnss_replay_ddm). A reflected ray with a carrier offset (synth.add_ray's
+    fade_hz) cancels in replay_coherent's zero-offset sum; here it stands at (its delay, its
+    offset), with the sign.
+
+    `taps_out` [n, 2, n_taps, max_rows] as replay_correlate returns it: a numpy array (the host
+    path, no GPU needed) or a torch tensor on the context's device, read where it lies by the
+    kernel. `rows`: the replay table the sums came from (n_rows, pos_bytes, numSample: the rows'
+    times). `u` [n_taps]: the taps' coordinates in chips (for replayed sums the tap offsets);
+    `prompt`: the tap whose I gives a row's sign, None for the one tap with u == 0, -1 for no sign
+    wipe. excl_chips / excl_hz: the secondary peak is the largest cell at least excl_chips OR at
+    least excl_hz away from the peak.
+
+    Returns a namespace: n_win [n]; per name a list of n arrays with one value per window --
+    peak_tap, peak_bin, peak_chips, peak_hz, peak_pow, sec_tap, sec_bin, sec_chips, sec_hz, sec_pow
+    (-1 / NaN where there is none); map, with want_map a list of n arrays [n_win, 2, n_dopp,
+    n_taps] (ZI then ZQ), or with device_out one torch tensor [n, cap, 2, n_dopp, n_taps] that
+    never left the device; u, dopp_hz, prompt and kernel_ms (0 on the host path)."""
+    uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    hz = np.ascontiguousarray(dopp_hz, dtype=np.float64).reshape(-1)
+    nt, nd = len(uu), len(hz)
+    if prompt is None:
+        zero = np.flatnonzero(uu == 0)
+        if len(zero) != 1:
+            raise ValueError(f"replay_ddm: {len(zero)} taps have u == 0; name the prompt tap")
+        prompt = int(zero[0])
+    on_device = hasattr(taps_out, "data_ptr")
+    if device_out and not on_device:
+        raise ValueError("replay_ddm: device_out needs device sums (a torch tensor) and a Context")
+    if on_device:
+        if ctx is None:
+            raise ValueError("replay_ddm: a device tensor needs a Context")
+        torch = abi.require_torch()
+        t = taps_out
+        if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda or t.device.index != ctx.device:
+            raise ValueError("replay_ddm: the tensor is contiguous float64 on the context's device")
+        torch.cuda.current_stream(t.device).synchronize()
+        ptr = t.data_ptr()
+    else:
+        t = np.ascontiguousarray(taps_out, dtype=np.float64)
+        ptr = t.ctypes.data
+    if t.ndim != 4 or t.shape[1] != 2 or t.shape[2] != nt:
+        raise ValueError("replay_ddm: taps_out is [n, 2, n_taps, max_rows] with one u per tap")
+    n, max_rows = int(t.shape[0]), int(t.shape[3])
+    nr = np.ascontiguousarray(rows.n_rows, dtype=np.int64).reshape(-1)
+    pos = np.ascontiguousarray(rows.pos_bytes, dtype=np.int64)
+    ns = np.ascontiguousarray(rows.numSample, dtype=np.int64)
+    if len(nr) != n or pos.shape != (n, max_rows) or ns.shape != (n, max_rows):
+        raise ValueError("replay_ddm: rows.n_rows is [n], rows.pos_bytes and rows.numSample are [n][max_rows]")
+    cfg = abi.GnssReplayDdmCfg()
+    cfg.n, cfg.n_taps, cfg.prompt, cfg.rows_per_window, cfg.n_dopp = n, nt, int(prompt), int(rows_per_window), nd
+    cfg.dopp_hz, cfg.u = hz.ctypes.data, uu.ctypes.data
+    cfg.excl_chips, cfg.excl_hz, cfg.Fs = float(excl_chips), float(excl_hz), float(signal.Fs)
+    cfg.bytes_per_sample = int(file.dataPrecision) * int(file.dataType)
+    cfg.flags = (abi.OUT_DEVICE if on_device else 0) | (abi.DDM_MAP_DEVICE if device_out else 0)
+    src = abi.GnssReplayDdmIn()
+    src.taps, src.max_rows = ptr, max_rows
+    src.n_rows, src.pos_bytes, src.numSample = nr.ctypes.data, pos.ctypes.data, ns.ctypes.data
+    cap = max([int(k) // max(cfg.rows_per_window, 1) for k in nr] + [1])
+    out = abi.GnssReplayDdmOut()
+    out.cap = cap
+    n_win = np.zeros(max(n, 1), dtype=np.int64)
+    out.n_win = n_win.ctypes.data
+    ints = {f: np.full((max(n, 1), cap), -1, dtype=np.int32) for f in ("peak_bin", "peak_tap", "sec_bin", "sec_tap")}
+    pows = {f: np.full((max(n, 1), cap), np.nan) for f in ("peak_pow", "sec_pow")}
+    for f, a in {**ints, **pows}.items():
+        setattr(out, f, a.ctypes.data)
+    m = None
+    if device_out:
+        m = torch.zeros((n, cap, 2, nd, nt), dtype=torch.float64, device=f"cuda:{ctx.device}")
+        torch.cuda.current_stream(m.device).synchronize()
+        out.map = m.data_ptr()
+    elif want_map:
+        m = np.zeros((max(n, 1), cap, 2, nd, nt))
+        out.map = m.ctypes.data
+    lib = abi.load()
+    h = ctx.h if ctx is not None else None
+    st = lib.gnss_replay_ddm(h, C.byref(cfg), C.byref(src), C.byref(out))
+    if st != abi.OK:
+        msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
+        raise abi.GnssError(st, msg)
+    res = SimpleNamespace(n_win=n_win[:n].copy(), u=uu, dopp_hz=hz, prompt=int(prompt), kernel_ms=float(out.kernel_ms))
+    for f, a in {**ints, **pows}.items():
+        setattr(res, f, [a[c, : n_win[c]].copy() for c in range(n)])
+    for who in ("peak", "sec"):
+        tap, bin_ = getattr(res, who + "_tap"), getattr(res, who + "_bin")
+        setattr(res, who + "_chips", [np.where(x >= 0, uu[np.maximum(x, 0)], np.nan) for x in tap])
+        setattr(res, who + "_hz", [np.where(x >= 0, hz[np.maximum(x, 0)], np.nan) for x in bin_])
+    res.map = m if device_out or m is None else [m[c, : n_win[c]].copy() for c in range(n)]
+    return res

@@ -1251,6 +1251,98 @@ int gnss_acf_fit_taps(gnss_ctx *ctx, const gnss_acf_fit_taps_cfg *cfg,
 int gnss_acf_fit_taps_window(const gnss_acf_fit_taps_cfg *cfg, const double *zI, const double *zQ,
                              gnss_acf_fit_out *out);
 
+/* ---- delay-Doppler map over replayed rows (additive within ABI v14; detected by symbol) -------
+ * gnss_replay_correlate gives per-row complex sums on any tap grid with no loop closed, and a
+ * window's rows are contiguous in time. Summed coherently with one rotation per row they give the
+ * correlation the loop would have seen with its carrier nu Hz higher; for every (tap, nu) cell
+ * that is the delay-Doppler map of the window. A reflected ray whose carrier is offset from the
+ * direct one (gnss_synth_ray.fade_hz) rotates within the window and cancels in the zero-offset sum
+ * that gnss_acf_fit_taps fits; in the map it stands at (its delay, its offset), with the sign.
+ * csrc/replay_ddm.h is the one source of the arithmetic for host and device.
+ *
+ * Per channel c and window w of R = rows_per_window consecutive rows i0 = w*R .. i0+R-1 (only
+ * whole windows below n_rows[c] count), one value per tap j and per Doppler offset nu_m [Hz]:
+ *   - row time: s_i = (pos_bytes[i] - pos_bytes[i0]) / bytes_per_sample in int64,
+ *     t_i = ((double)(2*s_i + numSample[i] - 1) / 2.0) / Fs: the row's middle sample, in seconds
+ *     from the window's first sample. The host forms t once; both paths read that table.
+ *   - rotation: th = nu_m * t_i, r = th - rint(th), (sn, cs) = sin, cos of kRpTwoPi * r by
+ *     csrc/replay.h's rp_sincos; every operation rounds on its own (no contraction).
+ *   - sign: s_i from tap `prompt`'s I of the same row: >= 0 gives +1, anything else -1 (a NaN
+ *     gives -1): gnss_acf_fit_taps' rule. prompt = -1: no sign wipe (s_i = +1).
+ *   - cell: two plain left-to-right sums over the window's rows, ascending i, starting from 0:
+ *       ZI += s_i*(I*cs + Q*sn),  ZQ += s_i*(Q*cs - I*sn)
+ *     (s_i = +-1 is applied to I and Q first: the same bits, negation being exact). That is
+ *     (I + iQ) * exp(-i*2*pi*nu*t). The replay's wipe is I + iQ = i*conj(x*exp(iW)), so the cell is
+ *     the rows' sum with carrFreq + nu in place of carrFreq, the rotation held at each row's
+ *     middle sample. The loss inside a row is sinc(nu * T_row): 20 Hz on 1-ms rows loses 0.07 %.
+ *   - power: P = ZI*ZI + ZQ*ZQ, two rounded products and one add.
+ *   - peaks per window: cells are numbered bin-major, k = m*n_taps + j; a cell whose P is a NaN is
+ *     no candidate. The peak is the largest P, the lowest k among equals: peak_bin, peak_tap,
+ *     peak_pow. The secondary peak is the same rule over the cells with
+ *     |u[j] - u[peak_tap]| >= excl_chips OR |dopp_hz[m] - dopp_hz[peak_bin]| >= excl_hz:
+ *     sec_bin, sec_tap, sec_pow. No candidate: -1, -1, NaN.
+ * The sum order is fixed by the definition, not by the tiling: host and GPU give the same bits in
+ * every output, for any thread count, and a window's bits depend on that window alone. */
+#define GNSS_DDM_MAX_DOPP   256
+#define GNSS_DDM_MAP_DEVICE 2   /* with GNSS_OUT_DEVICE: out->map is DEVICE memory and stays there */
+typedef struct gnss_replay_ddm_cfg {
+    int32_t       n;                /* channels, 1..GNSS_MAX_SV                                 */
+    int32_t       n_taps;           /* 1..GNSS_REPLAY_MAX_TAPS                                  */
+    int32_t       prompt;           /* -1 (no sign wipe) or 0..n_taps-1                         */
+    int32_t       rows_per_window;  /* 2..4096                                                  */
+    int32_t       n_dopp;           /* 1..GNSS_DDM_MAX_DOPP                                     */
+    int32_t       flags;            /* 0, GNSS_OUT_DEVICE (in->taps is a DEVICE pointer), or
+                                       GNSS_OUT_DEVICE | GNSS_DDM_MAP_DEVICE                    */
+    const double *dopp_hz;          /* [n_dopp] host, finite, |nu| <= 1e5, in any order         */
+    const double *u;                /* [n_taps] host, tap coordinates in chips, finite          */
+    double        excl_chips;       /* >= 0                                                     */
+    double        excl_hz;          /* >= 0                                                     */
+    double        Fs;               /* > 0, finite                                              */
+    int32_t       bytes_per_sample; /* 1 or 2 (the record's dataType at int8)                   */
+    int32_t       reserved;
+} gnss_replay_ddm_cfg;
+
+typedef struct gnss_replay_ddm_in {
+    const double  *taps;        /* [n][2][n_taps][max_rows], gnss_replay_out.taps' layout: a host
+                                   array, or with GNSS_OUT_DEVICE device memory of the context's
+                                   device                                                       */
+    int64_t        max_rows;    /* >= 1                                                         */
+    const int64_t *n_rows;      /* [n] host, each 0..max_rows                                   */
+    const int64_t *pos_bytes;   /* [n][max_rows] host: gnss_replay_rows' arrays                 */
+    const int64_t *numSample;   /* [n][max_rows] host, 1..2^22 in the rows of whole windows     */
+} gnss_replay_ddm_in;
+
+typedef struct gnss_replay_ddm_out {
+    int64_t  cap;        /* windows per channel the arrays hold                                 */
+    double  *map;        /* [n][cap][2][n_dopp][n_taps]: ZI then ZQ; NULL: peaks only. Device
+                            memory of the context's device with GNSS_DDM_MAP_DEVICE             */
+    int32_t *peak_bin;   /* [n][cap] each of the six; windows >= n_win[c] are left untouched    */
+    int32_t *peak_tap;
+    double  *peak_pow;
+    int32_t *sec_bin;
+    int32_t *sec_tap;
+    double  *sec_pow;
+    int64_t *n_win;      /* [n] out: n_rows[c] / rows_per_window                                */
+    double   kernel_ms;  /* out: hipEvents around the kernels; 0 on the host path               */
+} gnss_replay_ddm_out;
+
+/* Host sums need no GPU and ctx may be NULL: up to 16 threads, a window by one thread. With
+ * GNSS_OUT_DEVICE the map is formed on the GPU (csrc/replay_ddm.hip: one workgroup per window,
+ * tile of bins and tile of taps, then one per window for the peaks) and downloaded, or left in
+ * out->map with GNSS_DDM_MAP_DEVICE. Everything is checked on the host before any launch; a
+ * refusal sets the error text and leaves the outputs untouched and the context usable.
+ * GNSS_EARG: a null argument (map excepted), n, n_taps, prompt, rows_per_window or n_dopp out of
+ * range, a non-finite u[j] or dopp_hz[m], |dopp_hz[m]| > 1e5, a negative or NaN excl_chips or
+ * excl_hz, Fs, bytes_per_sample, max_rows < 1, cap < 0, n_rows[c] outside 0..max_rows, more
+ * windows than cap, numSample outside 1..2^22 in a window's row, an unknown flag,
+ * GNSS_DDM_MAP_DEVICE without GNSS_OUT_DEVICE or without a map, GNSS_OUT_DEVICE without a context
+ * or with taps (or the device map) that is not device memory of the context's device, and a
+ * context of gnss_ctx_create_multi. GNSS_EIO: within a window a negative pos_bytes, one that is
+ * lower than the row's before, or a difference to the window's first row that is no multiple of
+ * bytes_per_sample or exceeds 2^50 bytes. */
+int gnss_replay_ddm(gnss_ctx *ctx, const gnss_replay_ddm_cfg *cfg, const gnss_replay_ddm_in *in,
+                    gnss_replay_ddm_out *out);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
