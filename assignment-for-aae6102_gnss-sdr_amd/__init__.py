@@ -16,7 +16,7 @@ from .sdr import (Context, DeviceRecord, DeviceTrackOutBuffers, StructArray, Tra
                   trackingVT_POS_updated_multicorrelator, trackingVT_mc_run, trackingVT_mc_step, vt_channel,
                   NavSolCtBuffers, ct_positioning, findPosSV, trackingCT_POS_updated, acf_features, acf_fit, CalculateFeatures,
                   scene_labels, feature_table, KnnModel, knn_train, knn_classify, confusion, replay_rows, replay_correlate,
-                  replay_coherent, acf_fit_taps, replay_fit, replay_ddm)
+                  replay_coherent, acf_fit_taps, replay_fit, replay_ddm, acf_fit_multi, replay_fit_multi)
 
 __all__ = ["abi", "synth", "Context", "DeviceRecord", "DeviceTrackOutBuffers", "StructArray", "TrackOutBuffers",
            "acquisition", "ca_code", "colon", "default_context", "initParameters", "naviDecode_updated",
@@ -24,4 +24,5 @@ __all__ = ["abi", "synth", "Context", "DeviceRecord", "DeviceTrackOutBuffers", "
            "trackingVT_POS_updated_multicorrelator", "trackingVT_mc_run", "trackingVT_mc_step", "vt_channel",
            "NavSolCtBuffers", "ct_positioning", "findPosSV", "trackingCT_POS_updated", "acf_features", "acf_fit",
            "CalculateFeatures", "scene_labels", "feature_table", "KnnModel", "knn_train", "knn_classify", "confusion",
-           "replay_rows", "replay_correlate", "replay_coherent", "acf_fit_taps", "replay_fit", "replay_ddm"]
+           "replay_rows", "replay_correlate", "replay_coherent", "acf_fit_taps", "replay_fit", "replay_ddm",
+           "acf_fit_multi", "replay_fit_multi"]

@@ -358,6 +358,30 @@ class GnssReplayDdmOut(C.Structure):
 ADDED_STRUCTS.update({"gnss_replay_ddm_cfg": "GnssReplayDdmCfg", "gnss_replay_ddm_in": "GnssReplayDdmIn",
                       "gnss_replay_ddm_out": "GnssReplayDdmOut"})
 
+# The multi-ray fit on any tap grid (gnss_acf_fit_multi / gnss_acf_fit_multi_window; additive within
+# ABI v14): up to ACF_MULTI_MAX_PATHS paths by alternating projection on the candidate grid q; the
+# input is gnss_acf_fit_taps' (GnssAcfFitTapsIn, u, prompt). q_min..: -2.4..0.4, what the replay grid
+# -2.5:0.05:1.0 can carry
+ACF_MULTI_MAX_PATHS = 4
+ACF_FIT_MULTI_DEFAULTS = dict(ind_start=1, numOverLap=100, q_min=-2.40, q_step=0.01, q_count=281, max_paths=3,
+                              sweeps=4, sep_min=5, gain_min=16.0)
+
+
+class GnssAcfFitMultiCfg(C.Structure):
+    _fields_ = [("n", C.c_int32), ("ind_start", C.c_int32), ("numOverLap", C.c_int32), ("n_taps", C.c_int32),
+                ("prompt", C.c_int32), ("flags", C.c_int32), ("u", C.c_void_p), ("q_min", C.c_double),
+                ("q_step", C.c_double), ("q_count", C.c_int32), ("max_paths", C.c_int32), ("sweeps", C.c_int32),
+                ("sep_min", C.c_int32), ("gain_min", C.c_double)]
+
+
+class GnssAcfFitMultiOut(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("windows", C.POINTER(C.c_int64)), ("paths", C.POINTER(C.c_int32)),
+                ("searches", C.POINTER(C.c_int32))] + \
+               [(f, C.POINTER(C.c_double)) for f in ("bias", "q", "A_re", "A_im", "res", "energy", "zI", "zQ")]
+
+
+ADDED_STRUCTS.update({"gnss_acf_fit_multi_cfg": "GnssAcfFitMultiCfg", "gnss_acf_fit_multi_out": "GnssAcfFitMultiOut"})
+
 
 class GnssSynthSv(C.Structure):
     _fields_ = [("prn", C.c_int32), ("doppler_hz", C.c_double), ("code_phase0", C.c_double),
@@ -513,6 +537,11 @@ PROTOTYPES = {
     # the delay-Doppler map over replayed rows (additive within ABI v14: detected by symbol)
     "gnss_replay_ddm": (C.c_int, [C.c_void_p, C.POINTER(GnssReplayDdmCfg), C.POINTER(GnssReplayDdmIn),
                                   C.POINTER(GnssReplayDdmOut)]),
+    # the multi-ray fit on any tap grid (additive within ABI v14: detected by symbol)
+    "gnss_acf_fit_multi": (C.c_int, [C.c_void_p, C.POINTER(GnssAcfFitMultiCfg), C.POINTER(GnssAcfFitTapsIn),
+                                     C.POINTER(GnssAcfFitMultiOut)]),
+    "gnss_acf_fit_multi_window": (C.c_int, [C.POINTER(GnssAcfFitMultiCfg), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.POINTER(GnssAcfFitMultiOut)]),
     "gnss_lane_boundaries": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double]),
     "gnss_ctx_lane_path": (C.c_int, [C.c_void_p]),
 }

@@ -24,35 +24,12 @@
 #include <hip/hip_runtime.h>
 
 #include "acf_fit_taps.h"
+#include "acf_fit_taps_dev.h"
 
 namespace gnss {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kTile = 64;           // rows per LDS tile: one wave's load of one series
-constexpr int kStride = kTile + 1;  // doubles; odd: lanes along the series hit distinct banks
-constexpr int kGroup = 64;          // series per LDS tile: one wave adds them
-
-// the block's minimum of the lanes' (res, index), valid in lane 0 of the block; `wres` / `wh`
-// hold one entry per wave and are free again on return
-__device__ AcfFttBest block_best(AcfFttBest b, double* wres, int* wh)
-{
-    for (int off = 32; off; off >>= 1) {
-        const double r = __shfl_xor(b.res, off);
-        const int h = __shfl_xor(b.h, off);
-        ftt_best_merge(b, r, h);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        wres[threadIdx.x >> 6] = b.res;
-        wh[threadIdx.x >> 6] = b.h;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int v = 1; v < kWaves; v++) ftt_best_merge(b, wres[v], wh[v]);
-    __syncthreads();
-    return b;
-}
+using namespace fttdev;  // stage 1 and the block's minimum, shared with acf_fit_multi.hip
 
 // window blockIdx.x of all channels' windows in channel order; its rows lie below n_rows[c] <=
 // max_rows (host check), so every load is inside channel c's series
@@ -77,24 +54,7 @@ __global__ __launch_bounds__(kThreads) void acf_fit_taps_kernel(AcfFttDev d)
     const int N = (int)d.numOverLap;
 
     // stage 1
-    for (int t0 = 0; t0 < N; t0 += kTile) {
-        const int nr = N - t0 < kTile ? N - t0 : kTile;
-        if (tid < nr) sg[tid] = ftt_sign(base[(int64_t)d.grid.prompt * d.max_rows + t0 + tid]);
-        for (int s0 = 0; s0 < S; s0 += kGroup) {
-            const int ns = S - s0 < kGroup ? S - s0 : kGroup;
-            for (int i = tid; i < ns * kTile; i += kThreads) {
-                const int s = i / kTile, r = i % kTile;
-                if (r < nr) tile[s * kStride + r] = base[(int64_t)(s0 + s) * d.max_rows + t0 + r];
-            }
-            __syncthreads();  // (the signs too, in the row tile's first group)
-            if (tid < ns) {
-                double acc = t0 ? zs[s0 + tid] : 0.0;
-                for (int r = 0; r < nr; r++) acc = ftt_accum(acc, sg[r], tile[tid * kStride + r], t0 + r == 0);
-                zs[s0 + tid] = acc;
-            }
-            __syncthreads();
-        }
-    }
+    block_sums(base, d.max_rows, N, nt, d.grid.prompt, tile, sg, zs);
     for (int s = tid; s < S; s += kThreads)
         if (d.z) d.z[w * S + s] = zs[s];
     for (int j = tid; j < nt; j += kThreads) us[j] = d.u[j];

@@ -1906,6 +1906,119 @@ def replay_fit(file, signal, rows, taps, *, chip_off: int = 0, post=None, ctx: C
 
 
 # ---------------------------------------------------------------------------
+# The multi-ray fit on any tap grid (gnss_acf_fit_multi)
+# ---------------------------------------------------------------------------
+def acf_fit_multi(taps_out, n_rows, u, prompt=None, *, ctx: Context | None = None, want_acf: bool = False, **params):
+    """Up to four paths (the direct one and up to three rays) fitted to each window's coherently
+    summed correlation function at the coordinates `u` (gnss_acf_fit_multi): alternating
+    projection, a path's position searched on the grid q while the others stay, all amplitudes
+    solved jointly. Returns a namespace: windows [n] and, per name, a list of n arrays -- paths,
+    searches, bias, bias_m, energy [windows]; q, A_re, A_im, ratio, dphi_cycles, e [4][windows] (the
+    selected order's paths, the earliest arrival first, NaN beyond `paths`; ratio[k] = |A_k|/|A_0|,
+    dphi_cycles[k] the phase of A_k against A_0, e[k] = q[0] - q[k], the delay after the first
+    path); res [5][windows] (res[0] = energy, res[m] order m's residual, NaN if not formed); with
+    want_acf also zI, zQ [n_taps][windows] -- plus u, prompt and kernel_ms (0 on the host path).
+
+    `taps_out`, `n_rows`, `u`, `prompt`, `ctx`: as acf_fit_taps (a numpy array runs the host path, a
+    torch tensor on the context's device the kernel, which reads the sums where they lie). params:
+    ind_start, numOverLap, q_min, q_step, q_count, max_paths, sweeps, sep_min, gain_min
+    (abi.ACF_FIT_MULTI_DEFAULTS); cSpeed and codeFreqBasis for bias_m."""
+    cSpeed = float(params.pop("cSpeed", 299792458.0))
+    codeFreqBasis = float(params.pop("codeFreqBasis", 1.023e6))
+    unknown = set(params) - set(abi.ACF_FIT_MULTI_DEFAULTS)
+    if unknown:
+        raise TypeError(f"acf_fit_multi: unknown parameter(s) {sorted(unknown)}")
+    par = dict(abi.ACF_FIT_MULTI_DEFAULTS, **params)
+    uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    nt = len(uu)
+    if prompt is None:
+        zero = np.flatnonzero(uu == 0)
+        if len(zero) != 1:
+            raise ValueError(f"acf_fit_multi: {len(zero)} taps have u == 0; name the prompt tap")
+        prompt = int(zero[0])
+    on_device = hasattr(taps_out, "data_ptr")
+    if on_device:
+        if ctx is None:
+            raise ValueError("acf_fit_multi: a device tensor needs a Context")
+        torch = abi.require_torch()
+        t = taps_out
+        if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda or t.device.index != ctx.device:
+            raise ValueError("acf_fit_multi: the tensor is contiguous float64 on the context's device")
+        torch.cuda.current_stream(t.device).synchronize()
+        ptr = t.data_ptr()
+    else:
+        t = np.ascontiguousarray(taps_out, dtype=np.float64)
+        ptr = t.ctypes.data
+    if t.ndim != 4 or t.shape[1] != 2 or t.shape[2] != nt:
+        raise ValueError("acf_fit_multi: taps_out is [n, 2, n_taps, max_rows] with one u per tap")
+    n, max_rows = int(t.shape[0]), int(t.shape[3])
+    if n > abi.VT_MAX_CH:
+        raise ValueError(f"acf_fit_multi takes at most {abi.VT_MAX_CH} channels")
+    nr = np.ascontiguousarray(n_rows, dtype=np.int64).reshape(-1)
+    if len(nr) != n:
+        raise ValueError("acf_fit_multi: n_rows has one value per channel")
+    cfg = abi.GnssAcfFitMultiCfg()
+    cfg.n, cfg.n_taps, cfg.prompt = n, nt, int(prompt)
+    cfg.u = uu.ctypes.data
+    cfg.flags = abi.OUT_DEVICE if on_device else 0
+    for k in ("ind_start", "numOverLap", "q_count", "max_paths", "sweeps", "sep_min"):
+        setattr(cfg, k, int(par[k]))
+    for k in ("q_min", "q_step", "gain_min"):
+        setattr(cfg, k, float(par[k]))
+    src = abi.GnssAcfFitTapsIn()
+    src.taps, src.max_rows, src.n_rows = ptr, max_rows, nr.ctypes.data
+    nov = max(cfg.numOverLap, 1)
+    cap = max([max(int(l) - cfg.ind_start, 0) // nov for l in nr] + [1])
+    P, nn = abi.ACF_MULTI_MAX_PATHS, max(n, 1)
+    out = abi.GnssAcfFitMultiOut()
+    out.cap = cap
+    windows = np.zeros(nn, dtype=np.int64)
+    out.windows = windows.ctypes.data_as(C.POINTER(C.c_int64))
+    ints = {f: np.zeros((nn, cap), dtype=np.int32) for f in ("paths", "searches")}
+    for f, a in ints.items():
+        setattr(out, f, a.ctypes.data_as(C.POINTER(C.c_int32)))
+    arr = {"bias": np.zeros((nn, cap)), "energy": np.zeros((nn, cap)), "res": np.zeros((nn, P + 1, cap))}
+    arr.update({f: np.zeros((nn, P, cap)) for f in ("q", "A_re", "A_im")})
+    if want_acf:
+        arr["zI"], arr["zQ"] = np.zeros((nn, nt, cap)), np.zeros((nn, nt, cap))
+    for f, a in arr.items():
+        setattr(out, f, a.ctypes.data_as(C.POINTER(C.c_double)))
+    lib = abi.load()
+    h = ctx.h if ctx is not None else None
+    st = lib.gnss_acf_fit_multi(h, C.byref(cfg), C.byref(src), C.byref(out))
+    if st != abi.OK:
+        msg = (lib.gnss_last_error(h) or b"").decode() if h else lib.gnss_strerror(st).decode()
+        raise abi.GnssError(st, msg)
+    res = SimpleNamespace(windows=windows[:n].copy(), u=uu, prompt=int(prompt),
+                          kernel_ms=float(ctx.timing()["track_kernel_ms"]) if on_device else 0.0)
+    for f, a in {**ints, **arr}.items():
+        setattr(res, f, [a[c, ..., : windows[c]].copy() for c in range(n)])
+    res.bias_m, res.ratio, res.dphi_cycles, res.e = [], [], [], []
+    for c in range(n):
+        a = res.A_re[c] + 1j * res.A_im[c]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            res.bias_m.append(res.bias[c] * cSpeed / codeFreqBasis)
+            res.ratio.append(np.abs(a) / np.abs(a[0]))
+            res.dphi_cycles.append(np.angle(a * np.conj(a[0])) / (2 * np.pi))
+            res.e.append(res.q[c][0] - res.q[c])
+    return res
+
+
+def replay_fit_multi(file, signal, rows, taps, *, chip_off: int = 0, post=None, ctx: Context | None = None, **params):
+    """replay_correlate on `taps`, then acf_fit_multi with u = taps on the replayed sums: several
+    rays on a grid of the caller's choice. With a Context both steps run on the GPU and the sums
+    stay in HBM between them (GNSS_OUT_DEVICE): only the fit rows come back. Returns acf_fit_multi's
+    namespace with kernel_ms = (the replay's, the fit's). params: acf_fit_multi's (prompt, want_acf,
+    the windows, the grid and the search parameters)."""
+    tp = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+    sums, replay_ms = replay_correlate(file, signal, rows, tp, chip_off=chip_off, post=post, ctx=ctx,
+                                       device_out=ctx is not None)
+    res = acf_fit_multi(sums, rows.n_rows, tp, params.pop("prompt", None), ctx=ctx, **params)
+    res.kernel_ms = (float(replay_ms), res.kernel_ms)
+    return res
+
+
+# ---------------------------------------------------------------------------
 # The delay-Doppler map over replayed rows (gnss_replay_ddm)
 # ---------------------------------------------------------------------------
 def replay_ddm(taps_out, rows, dopp_hz, *, u, prompt, rows_per_window: int, signal, file, ctx: Context | None = None,

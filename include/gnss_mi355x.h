@@ -1343,6 +1343,98 @@ typedef struct gnss_replay_ddm_out {
 int gnss_replay_ddm(gnss_ctx *ctx, const gnss_replay_ddm_cfg *cfg, const gnss_replay_ddm_in *in,
                     gnss_replay_ddm_out *out);
 
+/* ---- multi-ray fit of an ACF on any tap grid (additive within ABI v14; detected by symbol) ----
+ * gnss_acf_fit_taps fits one reflected path on an exhaustive (p, e) grid, which cannot grow to a
+ * third path. This fit adds paths one at a time by alternating projection (the family MEDLL
+ * belongs to): a path's position is searched on a 1-D grid while the others stay fixed, and the
+ * amplitudes of all paths are solved jointly for every candidate. Up to GNSS_ACF_MULTI_MAX_PATHS
+ * paths, the direct one included. The input is gnss_acf_fit_taps' (gnss_acf_fit_taps_in plus u and
+ * prompt), so replayed sums and the 25-tap records go in alike. All arithmetic is fp64, every
+ * operation rounded on its own, every sum over all n_taps taps left to right from its first term;
+ * csrc/acf_fit_multi.h is the one source for host and device and fixes the order of every
+ * operation of step 3.
+ *  1. Windows, the rows' signs, the coherent vector z = zI + j zQ and energy = sum_j |z_j|^2 are
+ *     exactly gnss_acf_fit_taps'. A non-finite z gives paths = 0, searches = 0 and every floating
+ *     output of the window NaN.
+ *  2. Candidate positions q_i = q_min + i*q_step, i < q_count, with r_i[j] = R(u[j] - q_i),
+ *     R(x) = max(0, 1 - |x|), in orient = +1's convention: a path that arrives later sits at a
+ *     lower q. A candidate is usable iff sum_j r_i[j]^2 != 0.
+ *  3. The joint fit of an ordered set of m positions (slots 1..m, m <= 4): G_kl = sum_j
+ *     r_k[j]*r_l[j], h_k = sum_j r_k[j]*z[j] (I and Q apart); Gaussian elimination without pivoting
+ *     in slot order (f = G_ik / d_k; G_il = G_il - f*G_kl for l > k; h_i = h_i - f*h_k), then
+ *     back-substitution (s = h_k; s = s - G_kl*A_l for l = k+1..m ascending; A_k = s / d_k). The
+ *     set is singular when a pivot fails d_k > (1e-9*G_kk), G_kk the original diagonal. res =
+ *     sum_j |((z_j - A_1 r_1j) - A_2 r_2j) - ...|^2. For m = 1 these are the operations of
+ *     gnss_acf_fit_taps' one-path hypothesis (A = h/a).
+ *  4. Search(k): the other slots fixed, every candidate i is tried in slot k's place, the slot order
+ *     kept. Skipped: an unusable i, an i with |i - i_l| < sep_min for another slot l, a singular
+ *     set. The lexicographic minimum of (res, i) wins and slot k moves there; a NaN never wins. If
+ *     nothing survives the slot stays; when that happens to a slot being appended, that order is
+ *     not formed and the orders end there. In a sweep the slot's present position is itself a
+ *     survivor, so a sweep never raises res beyond rounding.
+ *  5. Orders m = 1..max_paths: slot m is appended with Search(m); then up to `sweeps` rounds, each
+ *     Search(1) .. Search(m) in order, a round that moved no slot ending the rounds. The order keeps
+ *     its positions and res_m, the last winner's residual; res_0 = energy. `searches` counts the
+ *     Search calls of the window: it pins the path taken, not only where it ends.
+ *  6. paths = the largest formed m with res_{m-1} > gain_min*res_m (the last significant drop: with
+ *     two rays an intermediate order may explain little, and a sequential test would stop there);
+ *     1 if no m passes but order 1 was formed; 0 if order 1 was not formed (then q, A and bias are
+ *     NaN; res[0] and energy are given).
+ *  7. Outputs per window: paths; the selected order's paths by descending q (earliest arrival
+ *     first) with the joint amplitudes formed again from its positions: q[k], A_re[k], A_im[k] for
+ *     k < paths, NaN beyond; bias = q[0]; res[0..4], every order formed, NaN otherwise; energy;
+ *     searches; optionally zI / zQ, which equal gnss_acf_fit_taps' bit for bit. */
+#define GNSS_ACF_MULTI_MAX_PATHS 4
+
+typedef struct gnss_acf_fit_multi_cfg {
+    int32_t       n;            /* channels, 1..GNSS_VT_MAX_CH                                  */
+    int32_t       ind_start;    /* as gnss_acf_cfg, >= 1; default 1                             */
+    int32_t       numOverLap;   /* rows per window, 2..4096; default 100                        */
+    int32_t       n_taps;       /* 1..GNSS_REPLAY_MAX_TAPS                                      */
+    int32_t       prompt;       /* 0..n_taps-1                                                  */
+    int32_t       flags;        /* GNSS_OUT_DEVICE: in->taps is a DEVICE pointer, or 0          */
+    const double *u;            /* [n_taps] tap coordinates in chips, host, finite              */
+    double        q_min, q_step;      /* default -2.40, 0.01; q_step > 0                        */
+    int32_t       q_count;      /* 1..4096; default 281 (-2.4..0.4: what -2.5:0.05:1.0 carries) */
+    int32_t       max_paths;    /* 1..GNSS_ACF_MULTI_MAX_PATHS; default 3                       */
+    int32_t       sweeps;       /* 0..16; default 4; 0 is the plain greedy order                */
+    int32_t       sep_min;      /* 1..q_count; default 5                                        */
+    double        gain_min;     /* >= 0; default 16.0, the existing fits' value                 */
+} gnss_acf_fit_multi_cfg;
+
+typedef struct gnss_acf_fit_multi_out {
+    int64_t  cap;               /* windows per channel the arrays hold                          */
+    int64_t *windows;           /* [n] windows written per channel                              */
+    int32_t *paths;             /* [n][cap]                                                     */
+    int32_t *searches;          /* [n][cap]                                                     */
+    double  *bias;              /* [n][cap]                                                     */
+    double  *q, *A_re, *A_im;   /* [n][4][cap], whatever max_paths is                           */
+    double  *res;               /* [n][5][cap]                                                  */
+    double  *energy;            /* [n][cap]                                                     */
+    double  *zI, *zQ;           /* optional (NULL: not wanted) [n][n_taps][cap]                 */
+} gnss_acf_fit_multi_out;
+
+/* The fit over the sums `in`. Host sums need no GPU and ctx may be NULL (up to 16 threads, a window
+ * by one thread: the bits do not depend on the thread count); with GNSS_OUT_DEVICE the fit runs on
+ * the GPU (csrc/acf_fit_multi.hip, one block per window) and gnss_last_timing's track_kernel_ms
+ * holds the kernel's duration. Both paths give the same bits in every output. Everything is checked
+ * on the host before any launch; each refusal sets the error text and leaves the outputs untouched
+ * and the context usable. GNSS_EARG for a null argument, n, n_taps or prompt out of range, a
+ * non-finite u[j], numOverLap outside 2..4096, ind_start < 1, a q_step that is not positive and
+ * finite, a non-finite q_min, q_count outside 1..4096, max_paths outside 1..4, sweeps outside 0..16,
+ * sep_min outside 1..q_count, a gain_min that is negative or NaN, max_rows < 1, n_rows[c] outside
+ * 0..max_rows, more windows than cap, an unknown flag, GNSS_OUT_DEVICE without a context or with
+ * taps that is not device memory of the context's device, and device sums on a context of
+ * gnss_ctx_create_multi. */
+int gnss_acf_fit_multi(gnss_ctx *ctx, const gnss_acf_fit_multi_cfg *cfg,
+                       const gnss_acf_fit_taps_in *in, gnss_acf_fit_multi_out *out);
+
+/* The fit alone on one coherent vector zI[n_taps], zQ[n_taps], host only: cfg's n_taps, u, grid and
+ * search parameters are read (n, ind_start, numOverLap, prompt beyond its range check and flags are
+ * not); out with cap >= 1 gets window 0 of channel 0, zI / zQ, if given, the vector at [j * cap]. */
+int gnss_acf_fit_multi_window(const gnss_acf_fit_multi_cfg *cfg, const double *zI, const double *zQ,
+                              gnss_acf_fit_multi_out *out);
+
 /* generateCAcode.m:16-64: the 1023 +-1 chips of PRN 1..51 used by the kernels. */
 int gnss_ca_code(int prn, int8_t *out1023);
 
