@@ -348,17 +348,10 @@ inline void fmm_window(const AcfFmmPar& p, const double* u, const double* zI, co
     fmm_row(p, w, rs, finite, formed, sel, searches, u, zI, zQ, row);
 }
 
-// What the kernel takes (acf_fit_multi.hip). Every extent was checked by the host, as for AcfFttDev.
+// What the kernel takes (acf_fit_multi.hip)
 struct AcfFmmDev {
-    const double* taps;  // [n][2][n_taps][max_rows]
-    const double* u;     // [n_taps]
-    int64_t max_rows;
-    int n;
-    int64_t win_base[kFttMaxCh + 1];  // windows before channel c; [n] = all of them (< 2^31)
-    int64_t ind_start, numOverLap;
+    AcfFttIo io;  // rows: [win_base[n]][kFmmRow]
     AcfFmmPar par;
-    double* rows;  // [win_base[n]][kFmmRow]
-    double* z;     // [win_base[n]][2][n_taps]: zI then zQ per window, or null
 };
 
 // One block per window on `stream` (a hipStream_t) of the current device. Returns the hipError_t

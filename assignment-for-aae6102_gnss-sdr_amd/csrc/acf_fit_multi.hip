@@ -58,8 +58,7 @@ struct BlockOps {
     __device__ void sync() { __syncthreads(); }
 };
 
-// window blockIdx.x of all channels' windows in channel order; its rows lie below n_rows[c] <=
-// max_rows (host check), so every load is inside channel c's series
+// window blockIdx.x of all channels' windows in channel order (block_window)
 __global__ __launch_bounds__(kThreads) void acf_fit_multi_kernel(AcfFmmDev d)
 {
     __shared__ double tile[kGroup * kStride];
@@ -72,20 +71,10 @@ __global__ __launch_bounds__(kThreads) void acf_fit_multi_kernel(AcfFmmDev d)
     __shared__ int wh[kWaves];
 
     const int tid = threadIdx.x;
-    const int64_t w = blockIdx.x;
-    int c = 0;
-    while (c + 1 < d.n && w >= d.win_base[c + 1]) c++;
-    const int64_t m = w - d.win_base[c];
-    const int64_t row = ftt_window_row(m, d.ind_start, d.numOverLap);
     const int nt = d.par.n_taps;
-    const int S = 2 * nt;
-    const double* base = d.taps + (int64_t)c * S * d.max_rows + row;
 
     // stage 1
-    block_sums(base, d.max_rows, (int)d.numOverLap, nt, d.par.prompt, tile, sg, zs);
-    for (int s = tid; s < S; s += kThreads)
-        if (d.z) d.z[w * S + s] = zs[s];
-    for (int j = tid; j < nt; j += kThreads) us[j] = d.u[j];
+    block_window(d.io, nt, d.par.prompt, tile, sg, zs, us);
     for (int i = tid; i < kFmmMaxPaths * nt; i += kThreads) rs[i] = 0.0;
     if (tid < kFmmMaxPaths) work.pos[tid] = 0;  // (a slot's row and index are read, and masked, before it is placed)
     __syncthreads();
@@ -105,7 +94,8 @@ __global__ __launch_bounds__(kThreads) void acf_fit_multi_kernel(AcfFmmDev d)
         fmm_sys_fill(work, rs, sel, -1, nt, zI, zQ, tid, kThreads);
         __syncthreads();
     }
-    if (tid == 0) fmm_row(d.par, work, rs, finite, formed, sel, searches, us, zI, zQ, d.rows + w * kFmmRow);
+    if (tid == 0) fmm_row(d.par, work, rs, finite, formed, sel, searches, us, zI, zQ,
+                          d.io.rows + (int64_t)blockIdx.x * kFmmRow);
 }
 
 }  // namespace
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void acf_fit_multi_kernel(AcfFmmDev d)
 int acf_fit_multi_launch(const AcfFmmDev& d, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int64_t total = d.win_base[d.n];
+    const int64_t total = d.io.win_base[d.io.n];
     if (total > 0) hipLaunchKernelGGL(acf_fit_multi_kernel, dim3((unsigned)total), dim3(kThreads), 0, stream, d);
     return (int)hipGetLastError();
 }

@@ -6,10 +6,11 @@
 // right from its first term, the skip rules, the lexicographic minimum of (res, index), the
 // winners formed again from their indices, paths = 0 / 1 / 2 and the NaN outputs. With n_taps =
 // 25, prompt = 12 and u[j] = (orient*(j-12))*corrSpacing every output equals gnss_acf_fit's bit
-// for bit. acf_fit.h itself is left as it is: its kernel keeps the 25 taps in registers, which a
-// run-time tap count cannot.
-// One source for the arithmetic, called in loops by the host path (acf_fit_taps.cpp) and by the
-// kernel (acf_fit_taps.hip), compiled without contraction and without fast-math on both sides.
+// for bit. acf_fit.h itself is left as it is for its kernel, whose tap count is a compile-time 25;
+// gnss_acf_fit's host path runs on this file (acf_fit.cpp).
+// One source for the arithmetic, called in loops by the host paths (acf_fit_host.h's driver for
+// acf_fit.cpp and acf_fit_taps.cpp) and by the kernel (acf_fit_taps.hip), compiled without
+// contraction and without fast-math on both sides.
 // No HIP include and no project include: tests/native/acf_fit_taps_host.cpp calls these functions
 // on the CPU under AddressSanitizer and UBSan.
 #pragma once
@@ -277,18 +278,24 @@ GNSS_FTT_HD AcfFttRow ftt_window(const AcfFttGrid& g, const double* u, const dou
     return ftt_select(g, u, zI, zQ, b1.h, b2.h);
 }
 
-// What the kernel takes (acf_fit_taps.hip). Every extent was checked by the host: the rows of
-// channel c's windows lie below n_rows[c] <= max_rows, n_taps in 1..kFttMaxTaps, prompt below it.
-struct AcfFttDev {
+// What a kernel over these sums takes beside its own parameters (acf_fit_taps.hip,
+// acf_fit_multi.hip); the host driver fills it (acf_fit_host.h). Every extent was checked there: the
+// rows of channel c's windows lie below n_rows[c] <= max_rows, n_taps in 1..kFttMaxTaps, prompt
+// below it.
+struct AcfFttIo {
     const double* taps;  // [n][2][n_taps][max_rows]
     const double* u;     // [n_taps]
     int64_t max_rows;
     int n;
     int64_t win_base[kFttMaxCh + 1];  // windows before channel c; [n] = all of them (< 2^31)
     int64_t ind_start, numOverLap;
-    AcfFttGrid grid;
-    double* rows;  // [win_base[n]][kFttRow]
+    double* rows;  // [win_base[n]][the kernel's doubles per window]
     double* z;     // [win_base[n]][2][n_taps]: zI then zQ per window, or null
+};
+
+struct AcfFttDev {
+    AcfFttIo io;
+    AcfFttGrid grid;
 };
 
 // One block per window on `stream` (a hipStream_t) of the current device. Returns the hipError_t

@@ -31,8 +31,7 @@ namespace {
 
 using namespace fttdev;  // stage 1 and the block's minimum, shared with acf_fit_multi.hip
 
-// window blockIdx.x of all channels' windows in channel order; its rows lie below n_rows[c] <=
-// max_rows (host check), so every load is inside channel c's series
+// window blockIdx.x of all channels' windows in channel order (block_window)
 __global__ __launch_bounds__(kThreads) void acf_fit_taps_kernel(AcfFttDev d)
 {
     __shared__ double tile[kGroup * kStride];
@@ -43,21 +42,10 @@ __global__ __launch_bounds__(kThreads) void acf_fit_taps_kernel(AcfFttDev d)
     __shared__ int wh[kWaves];
 
     const int tid = threadIdx.x;
-    const int64_t w = blockIdx.x;
-    int c = 0;
-    while (c + 1 < d.n && w >= d.win_base[c + 1]) c++;
-    const int64_t m = w - d.win_base[c];
-    const int64_t row = ftt_window_row(m, d.ind_start, d.numOverLap);
     const int nt = d.grid.n_taps;
-    const int S = 2 * nt;  // the series: I then Q of every tap
-    const double* base = d.taps + (int64_t)c * S * d.max_rows + row;
-    const int N = (int)d.numOverLap;
 
     // stage 1
-    block_sums(base, d.max_rows, N, nt, d.grid.prompt, tile, sg, zs);
-    for (int s = tid; s < S; s += kThreads)
-        if (d.z) d.z[w * S + s] = zs[s];
-    for (int j = tid; j < nt; j += kThreads) us[j] = d.u[j];
+    block_window(d.io, nt, d.grid.prompt, tile, sg, zs, us);
     __syncthreads();
 
     // stage 2
@@ -74,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void acf_fit_taps_kernel(AcfFttDev d)
     b1 = block_best(b1, wres, wh);
     b2 = block_best(b2, wres, wh);
     if (tid == 0) {
-        reinterpret_cast<AcfFttRow*>(d.rows)[w] = ftt_select(d.grid, us, zI, zQ, b1.h, b2.h);
+        reinterpret_cast<AcfFttRow*>(d.io.rows)[blockIdx.x] = ftt_select(d.grid, us, zI, zQ, b1.h, b2.h);
     }
 }
 
@@ -83,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void acf_fit_taps_kernel(AcfFttDev d)
 int acf_fit_taps_launch(const AcfFttDev& d, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int64_t total = d.win_base[d.n];
+    const int64_t total = d.io.win_base[d.io.n];
     if (total > 0) hipLaunchKernelGGL(acf_fit_taps_kernel, dim3((unsigned)total), dim3(kThreads), 0, stream, d);
     return (int)hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // acf_fit_taps_dev.h — what the kernels over [n][2][n_taps][max_rows] sums share (acf_fit_taps.hip,
-// acf_fit_multi.hip): a block's tiled coherent sums of one window and the block's minimum of the
-// lanes' (res, index). Device code, included by .hip files only, each compiled without contraction.
+// acf_fit_multi.hip): a block's tiled coherent sums of one window, the kernels' head around them
+// and the block's minimum of the lanes' (res, index). Device code, included by .hip files only,
+// each compiled without contraction.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,6 +48,26 @@ __device__ inline void block_sums(const double* base, int64_t max_rows, int N, i
             __syncthreads();
         }
     }
+}
+
+// A kernel's head, called by every lane: block blockIdx.x takes that window of all channels'
+// windows in channel order; its rows lie below n_rows[c] <= max_rows (host check), so every load
+// is inside channel c's series. The window's coherent sums into zs (block_sums) and, if wanted,
+// into d.z; the tap coordinates into us. us is complete for all after the caller's next barrier.
+__device__ inline void block_window(const AcfFttIo& d, int nt, int prompt, double* tile, double* sg, double* zs,
+                                    double* us)
+{
+    const int tid = threadIdx.x;
+    const int64_t w = blockIdx.x;
+    int c = 0;
+    while (c + 1 < d.n && w >= d.win_base[c + 1]) c++;
+    const int64_t row = ftt_window_row(w - d.win_base[c], d.ind_start, d.numOverLap);
+    const int S = 2 * nt;  // the series: I then Q of every tap
+    const double* base = d.taps + (int64_t)c * S * d.max_rows + row;
+    block_sums(base, d.max_rows, (int)d.numOverLap, nt, prompt, tile, sg, zs);
+    for (int s = tid; s < S; s += kThreads)
+        if (d.z) d.z[w * S + s] = zs[s];
+    for (int j = tid; j < nt; j += kThreads) us[j] = d.u[j];
 }
 
 // the wave's minimum of the lanes' (res, index) in every lane of the wave

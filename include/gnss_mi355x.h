@@ -982,7 +982,8 @@ int gnss_acf_twiddle(int32_t fft_n, double *c, double *s);
  * A multipath delay estimate per feature window: a direct path plus one reflected path fitted to
  * the coherently summed 25-tap correlation function. It goes beyond the reference, which has no
  * such estimator. All arithmetic fp64, every operation rounded on its own, every sum left to
- * right from its first term (csrc/acf_fit.h is the one source for host and device).
+ * right from its first term (csrc/acf_fit.h is the kernel's source; the host path runs the same
+ * functions at 25 taps from csrc/acf_fit_taps.h).
  *   - Windows: gnss_acf_features' (ind_start, numOverLap, the same count and rows), so fit row m
  *     of channel c lines up with feature row m.
  *   - Coherent vector: for row r of the window s_r = +1 if the prompt's I sum (tap 12 of 0..24) is

@@ -1,5 +1,6 @@
-// acf_fit_host.cpp -- csrc/acf_fit.h's functions (the arithmetic shared by the host path and the
-// kernel of gnss_acf_fit) on the CPU: built once plainly and once under AddressSanitizer and UBSan
+// acf_fit_host.cpp -- csrc/acf_fit.h's functions (the arithmetic of gnss_acf_fit's kernel; the host
+// path runs csrc/acf_fit_taps.h's twins of them, which tests/native/acf_fit_taps_host.cpp covers)
+// on the CPU: built once plainly and once under AddressSanitizer and UBSan
 // (tests/test_native_acf_fit.py). The vectors are heap arrays of exactly 25 elements, so a read
 // past a tap is an error there.
 #include <cmath>

@@ -1,6 +1,6 @@
 """The two-path fit of the 25-tap ACF through the C-ABI on host records (gnss_acf_fit with
-ctx = NULL and gnss_acf_fit_window; csrc/acf_fit.cpp over csrc/acf_fit.h): no GPU. The host path
-equals the numpy twin (acf_fit_twin.py) bit for bit in every output on seeded records over the
+ctx = NULL and gnss_acf_fit_window; csrc/acf_fit.cpp over csrc/acf_fit_taps.h at 25 taps): no GPU.
+The host path equals the numpy twin (acf_fit_twin.py) bit for bit in every output on seeded records over the
 window rule's lengths, both start rows, three window widths and two grids; the window counts are
 gnss_acf_features'; model vectors on grid points come back exactly; the selection, ratio_max, the
 sign wipe, ties and degenerate inputs, every GNSS_EARG case, and the Python wrapper."""
